@@ -4,16 +4,24 @@
 N=1 primary workload = BASELINE.json configs[1]: 100 M-row x 16-i64-column
 synthetic region, TableScan + Selection(col3 < k @10% selectivity) + count(*),
 on one MI355X. A "step" is one full pass of the fused scan/filter/agg hot
-path over the HBM-resident region. The default single-GPU invocation ALSO
-runs the secondary BASELINE workloads (cfg3 hash-agg, cfg4 CRC64 checksum)
-and attaches their full result objects under "secondary" in the same JSON
-line, each with its own metric text, roofline and cpu_baseline.
+path over the HBM-resident region. A plain run does only what that headline
+figure needs: generate + ingest the region, warm up, time --steps passes,
+print the result line.
 
-Parity gate (on by default at N=1): after warmup the full region is run
-through the CPU oracle and compared against the GPU response — bit-exact for
-cfg2/cfg4, order-insensitive grouped rows for cfg3 (group output order is
-not part of parity). The timed gate run doubles as the
-cpu_baseline sample.
+--full (single GPU) adds everything else the benchmark measures or checks:
+the secondary BASELINE workloads (cfg3 hash-agg, cfg4 CRC64 checksum), whose
+full result objects are attached under "secondary" in the same JSON line,
+each with its own metric text, roofline and cpu_baseline; and the parity
+gate: after warmup the full region is run through the CPU oracle and
+compared against the GPU response — bit-exact for cfg2/cfg4,
+order-insensitive grouped rows for cfg3 (group output order is not part of
+parity). The timed gate run doubles as the cpu_baseline
+sample.
+
+--dump-outputs DIR writes what the last timed step of the primary workload
+returned to its caller as DIR/<name>.npy (see dump_outputs). Inputs are a
+pure function of the arguments (copr_gen.cpp RNG contract), so two builds
+can be compared output for output.
 
 Multi-GPU: one process per GPU (torchrun), each rank owns its own Region
 shard (weak scaling — Regions are disjoint key ranges, exactly TiDB's
@@ -154,8 +162,47 @@ def read_traffic(workload, n_rows):
         return None
 
 
+DUMP_MAX_BYTES = 8 << 20          # response bytes kept (x4 as float32 = 32 MB)
+
+
+def dump_outputs(out_dir, workload, headline, data, n_out):
+    """Write the last timed step's caller-visible outputs as float .npy:
+
+    response_bytes.npy  f32  the encoded response, one element per byte
+                             (cfg4: the u64 checksum, 8 big-endian bytes).
+                             Grouped responses (cfg3/cfg5) are written with
+                             their rows sorted bytewise: group output order
+                             is not part of the contract.
+    n_rows.npy          f64  rows in the response (cfg4: KV pairs summed)
+    count.npy           f64  cfg2 only: the decoded count(*) (< 2^53, exact)
+
+    A response longer than DUMP_MAX_BYTES is sampled at fixed seeded
+    positions, so the files stay comparable between runs and under 64 MB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if workload == "cfg4":
+        data = int(headline).to_bytes(8, "big")
+    elif workload in ("cfg3", "cfg5"):
+        data = b"".join(sorted(split_datum_rows(
+            data, 5 if workload == "cfg3" else 3)))
+    b = np.frombuffer(data, dtype=np.uint8)
+    if b.size > DUMP_MAX_BYTES:
+        idx = np.random.default_rng(0).choice(
+            b.size, size=DUMP_MAX_BYTES, replace=False)
+        idx.sort()
+        b = b[idx]
+    np.save(os.path.join(out_dir, "response_bytes.npy"),
+            b.astype(np.float32))
+    np.save(os.path.join(out_dir, "n_rows.npy"),
+            np.array([n_out], dtype=np.float64))
+    if workload == "cfg2":
+        np.save(os.path.join(out_dir, "count.npy"),
+                np.array([headline], dtype=np.float64))
+
+
 def bench_one(tikv_amd, F, eng, workload, n_rows, steps, warmup,
-              world, rank, dist, have_cuda, parity, filter_offset=3):
+              world, rank, dist, have_cuda, parity, filter_offset=3,
+              dump_dir=None):
     """Run one workload end-to-end; returns the result dict (rank 0) and the
     merged headline count. Region/generator are freed before returning."""
     log("rank %d/%d: generating %d rows (%s shape)"
@@ -189,19 +236,23 @@ def bench_one(tikv_amd, F, eng, workload, n_rows, steps, warmup,
         algo_bytes = gen.key_bytes() + 8 * (gen.n_kv + 1)
 
     def step():
-        """one pass; returns (headline_count, raw_data, kernel_ns)"""
+        """one pass; returns (raw_data, n_out, kernel_ns): the response (or
+        the u64 checksum), its row count (KV pairs for cfg4), kernel time"""
         if workload == "cfg4":
             cs, kvs, byts = eng.checksum([rgn])
-            return cs, cs, 0
-        data, n, kns = eng.dag_run(req, [rgn])
-        if workload in ("cfg3", "cfg5"):
-            return n, data, kns
-        return parse_count(data), data, kns
+            return cs, kvs, 0
+        return eng.dag_run(req, [rgn])
+
+    def headline(data, n_out):
+        if workload == "cfg2":
+            return parse_count(data)
+        return data if workload == "cfg4" else n_out
 
     cnt = None
     g_data = None
     for _ in range(max(warmup, 1)):   # >=1: the parity gate needs a result
-        cnt, g_data, _ = step()
+        g_data, g_n, _ = step()
+        cnt = headline(g_data, g_n)
 
     # ---- full-scale parity gate (VERDICT r01: assert at BASELINE size).
     # The timed oracle pass doubles as the cpu_baseline sample (kind "port",
@@ -261,7 +312,7 @@ def bench_one(tikv_amd, F, eng, workload, n_rows, steps, warmup,
     kern_ns_total = 0
     t0 = time.perf_counter()
     for _ in range(steps):
-        _, _, kns = step()
+        last_data, last_n, kns = step()
         kern_ns_total += kns
     if have_cuda:
         torch.cuda.synchronize()
@@ -280,6 +331,11 @@ def bench_one(tikv_amd, F, eng, workload, n_rows, steps, warmup,
     if workload == "cfg4" or kern_s <= 0:
         kern_s = elapsed / steps     # checksum call is synchronous
     achieved_gbs = algo_bytes / kern_s / 1e9
+
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, workload, headline(last_data, last_n),
+                     last_data, last_n)
+        log("outputs of the last timed step written to %s" % dump_dir)
 
     result = None
     if rank == 0:
@@ -326,15 +382,25 @@ def main():
                     help="rows per GPU (dev override; BASELINE value default)")
     ap.add_argument("--filter-offset", type=int, default=3,
                     help="dev: which column offset the predicate filters")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity gate + cpu_baseline oracle "
+                         "pass and the secondary cfg3/cfg4 lines (N=1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs of the primary "
+                         "workload as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the parity gate + cpu_baseline oracle pass")
+                    help="with --full: skip the parity gate + cpu_baseline "
+                         "oracle pass")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary cfg3/cfg4 lines on default runs")
+                    help="with --full: skip the secondary cfg3/cfg4 lines")
     ap.add_argument("--workload", default=None,
                     choices=["cfg2", "cfg3", "cfg4", "cfg5"],
-                    help="bench ONLY this workload (default: cfg2 contract "
-                         "line + cfg3/cfg4 secondary lines at N=1)")
+                    help="bench ONLY this workload (default: the cfg2 "
+                         "contract line; --full attaches cfg3/cfg4 "
+                         "secondary lines at N=1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     # torch first: initialize HIP device discovery before the engine's own
     # runtime use in this process
@@ -370,23 +436,24 @@ def main():
         log("rank %d: engine RCCL communicator up (world %d)" % (rank, world))
 
     primary = args.workload or "cfg2"
-    # parity gate: oracle at full bench size is ~25-40 s of host CPU; the
-    # dev escape hatch is --no-cpu-baseline. cfg5's gate is covered by the
-    # GPU test suite instead (index parity tests).
-    parity = not args.no_cpu_baseline and primary != "cfg5"
+    # parity gate (--full): oracle at full bench size is ~25-40 s of host
+    # CPU; --no-cpu-baseline drops it from a --full run. cfg5's gate is
+    # covered by the GPU test suite instead (index parity tests).
+    gate = args.full and not args.no_cpu_baseline
+    parity = gate and primary != "cfg5"
     result = bench_one(tikv_amd, F, eng, primary, args.rows, args.steps,
                        args.warmup, world, rank, dist, have_cuda, parity,
-                       args.filter_offset)
+                       args.filter_offset, args.dump_outputs)
 
-    # secondary BASELINE lines (hash-agg + checksum) on the default
-    # single-process invocation — VERDICT r01: driver-measurable cfg3/cfg4
-    if (args.workload is None and world == 1 and not args.no_secondary):
+    # secondary BASELINE lines (hash-agg + checksum) on a single-process
+    # --full invocation — VERDICT r01: driver-measurable cfg3/cfg4
+    if (args.full and args.workload is None and world == 1
+            and not args.no_secondary):
         secondary = []
         for w in ("cfg3", "cfg4"):
             r = bench_one(tikv_amd, F, eng, w, args.rows,
                           max(args.steps // 2, 3), max(args.warmup // 2, 2),
-                          world, rank, dist, have_cuda,
-                          not args.no_cpu_baseline)
+                          world, rank, dist, have_cuda, gate)
             if r is not None:
                 secondary.append(r)
         if result is not None:

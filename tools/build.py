@@ -8,7 +8,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _make(path, target=None):
-    cmd = ["make", "-C", path, "-j", str(os.cpu_count() or 4)]
+    # a handful of translation units: more jobs than that buys nothing, and
+    # cpu_count() overstates what a shared build host hands one user
+    cmd = ["make", "-C", path, "-j", str(min(os.cpu_count() or 4, 16))]
     if target:
         cmd.append(target)
     r = subprocess.run(cmd, capture_output=True, text=True)
