@@ -94,6 +94,12 @@ copr_status copr_dag_run(copr_engine *, const CoprDagRequest *,
                          CoprSelectResult *out);
 void        copr_result_free(CoprSelectResult *);
 
+/* Diagnostics for the decoded column planes: how many
+ * per-region kernel launches of this engine read column planes instead of
+ * the row bytes, and how many planes it has built. Monotonic. */
+uint64_t    copr_engine_plane_launches(const copr_engine *);
+uint64_t    copr_engine_plane_builds(const copr_engine *);
+
 /* ---- checksum (REQ_TYPE_CHECKSUM = 105; src/coprocessor/checksum.rs:59-114) ----
  * CRC-64/XZ per KV over key||value, XOR-folded (order-independent). */
 copr_status copr_checksum(copr_engine *, copr_region *const *regions,

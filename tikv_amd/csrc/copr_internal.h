@@ -33,7 +33,29 @@ struct DevRegion {
      filter parse, the measured wall once DMA fully overlaps (the same idea
      row-v2 bakes into its format as the in-row offsets array). */
   uint8_t *d_celldir = nullptr;
+  /* decoded column planes: per column id, the column's value
+     and a state byte for every row, built lazily by the first plane-eligible
+     request that references the column and cached until the region is
+     destroyed. A slot with val == nullptr is a tombstone: the build found
+     the column unsuited (too many ROWPARSE rows) and is not repeated. */
+#define COPR_MAX_PLANES 16
+  struct ColPlane {
+    int64_t col_id = 0;
+    int64_t *val = nullptr;        /* [n_kv] (+ tail slack) */
+    uint8_t *st = nullptr;         /* [n_kv] (+ tail slack), PST_* */
+    uint64_t n_rowparse = 0;       /* rows left to query time (PST_ROWPARSE) */
+  };
+  ColPlane planes[COPR_MAX_PLANES];
+  int32_t n_planes = 0;
+  uint64_t plane_bytes = 0;        /* charged against the budget cap */
 };
+
+/* column-plane row states. ABSENT stays distinct from NULL because the
+   default fill differs per request; ROWPARSE defers to the row bytes at
+   query time (row-v2 cells decode by the request's signedness; cells that
+   are neither int, real nor NULL error or count depending on the consumer);
+   ERR = locating the column in this row fails, whoever asks. */
+enum { PST_INT = 0, PST_REAL, PST_NULL, PST_ABSENT, PST_ROWPARSE, PST_ERR };
 
 /* compare kinds (order matches oracle CmpKind) */
 enum { CMP_LT = 0, CMP_LE, CMP_GT, CMP_GE, CMP_EQ, CMP_NE };
@@ -237,6 +259,20 @@ struct SimpleAggAcc {
   unsigned long long sum_hi;     /* two's-complement high word */
 };
 
+/* planes a k_plane_agg launch consumes: the two filter channels and one per
+   aggregate (null val = channel unused); dir = the column's cell-directory
+   plane or null, consulted for ROWPARSE rows only */
+struct PlaneRef {
+  const int64_t *val;
+  const uint8_t *st;
+  const uint8_t *dir;
+  uint64_t n_rowparse;           /* 0 = no row of this plane needs the dir */
+};
+struct PlaneSet {
+  PlaneRef f, f2;
+  PlaneRef a[COPR_MAX_AGGS];
+};
+
 /* hash-agg table (device): parallel arrays.
  * keys[]: EMPTY sentinel = INT64_MIN bias — the real INT64_MIN key and the
  * NULL key get dedicated accumulator blocks (reserved[0]=int64_min,
@@ -279,6 +315,19 @@ int dev_crc64_launch(const DevRegion &rgn, const uint64_t *d_tables /*8*256*/,
 /* MVCC write-CF filter: builds a visible-row DevRegion from raw write-CF
  * arrays already on device. 0 ok, -1 malformed, -2 oom, -3 unsupported. */
 int dev_celldir_build(DevRegion &rgn, hipStream_t s);
+/* column planes. dev_colplane_get returns the region's plane slot for
+ * col_id, building it on first use (synchronous; callers build before their
+ * timed events). Null = no plane: budget_bytes exceeded, allocation failed,
+ * slots exhausted or the column tombstoned — the caller takes the scan
+ * path. *built is incremented when this call ran the build kernel. */
+const DevRegion::ColPlane *dev_colplane_get(DevRegion &rgn, int64_t col_id,
+                                            uint64_t budget_bytes,
+                                            hipStream_t s, uint64_t *built);
+void dev_colplane_free(DevRegion &rgn);
+/* simple aggregates (mode 1) over column planes instead of the row bytes */
+int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
+                         const DevRegion &rgn, SimpleAggAcc *d_simple,
+                         void *stream);
 int dev_stream_agg(const ScanPlan &plan, const DevRegion &rgn, void *stream,
                    std::vector<SimpleAggAcc> *h_accs,
                    std::vector<long long> *h_gk, std::vector<uint8_t> *h_gs);
@@ -353,6 +402,14 @@ struct copr_engine {
   uint32_t ht_cache_tsize = 0;
   int ht_cache_naggs = 0;
   bool ht_cache_ext = false;
+  /* simple-agg accumulators ([COPR_MAX_AGGS + 1] accs, [COPR_MAX_AGGS * 2]
+     high limbs): allocated on first use, re-zeroed per request with async
+     memsets, freed in engine destroy */
+  copr::SimpleAggAcc *d_simple_acc = nullptr;
+  unsigned long long *d_simple_ext = nullptr;
+  /* diagnostics (copr_engine_plane_launches / _builds) */
+  uint64_t plane_launches = 0;
+  uint64_t plane_builds = 0;
 };
 
 struct copr_region {

@@ -416,7 +416,7 @@ __device__ static inline bool next_cell(const uint8_t *vp, uint32_t vlen,
           uint64_t uv = (vm & 0x7f) | ((vm >> 8) & 0x7f) << 7 |
                         ((vm >> 16) & 0x7f) << 14 | ((vm >> 24) & 0x7f) << 21 |
                         ((vm >> 32) & 0x7f) << 28;
-          cv->is_null = false; cv->has_dec = false;
+          cv->is_null = false; cv->has_dec = false; cv->has_real = false;
           cv->has_int = true; cv->flag = (uint8_t)dflag;
           if (dflag == 8) {
             uint64_t h2 = uv >> 1;
@@ -431,6 +431,7 @@ __device__ static inline bool next_cell(const uint8_t *vp, uint32_t vlen,
         /* varint needs >5 bytes: generic datum parse below */
       } else if (dflag == 0) {
         cv->is_null = true; cv->has_int = false; cv->has_dec = false;
+        cv->has_real = false;
         cv->flag = 0; cv->len = 1;
         *pos = p + 3;
         return true;
@@ -1144,6 +1145,81 @@ __device__ static inline void atomic_add_i256(unsigned long long *lo,
   if (a3) atomicAdd(&ext[1], a3);
 }
 
+/* simple-agg epilogue shared by every mode-1 kernel: per-wave fold of the
+ * per-lane partials, then one atomic set per wave per aggregate into the
+ * request's accumulators. Must be reached by all 64 lanes of the wave. */
+template <int NAGGS>
+__device__ static inline void d_simple_epilogue(
+    const ScanPlan &plan, SimpleAggAcc *__restrict__ simple_acc,
+    const unsigned long long (&l_cnt)[NAGGS],
+    const unsigned long long (&l_lo)[NAGGS], const long long (&l_hi)[NAGGS]) {
+  #pragma unroll
+  for (int a = 0; a < NAGGS; a++) {
+    const int32_t kind = plan.aggs[a].kind;
+    unsigned long long c = l_cnt[a];
+    unsigned long long lo = l_lo[a];
+    long long hi = l_hi[a];
+    if (d_is_fold(kind)) {
+      for (int off = 32; off > 0; off >>= 1) {
+        c += (unsigned long long)__shfl_down((long long)c, off, 64);
+        unsigned long long plo =
+            (unsigned long long)__shfl_down((long long)lo, off, 64);
+        if (d_is_xor(kind)) lo ^= plo;
+        else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT || kind == DAGG_MAX_REAL || kind == DAGG_MIN_REAL)
+          lo = lo > plo ? lo : plo;
+        else lo |= plo;
+      }
+      if ((threadIdx.x & 63u) == 0) {
+        if (c) atomicAdd(&simple_acc[a].cnt, c);
+        if (lo) {
+          if (d_is_xor(kind)) atomicXor(&simple_acc[a].sum_lo, lo);
+          else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT || kind == DAGG_MAX_REAL || kind == DAGG_MIN_REAL)
+            atomicMax(&simple_acc[a].sum_lo, lo);
+          else atomicOr(&simple_acc[a].sum_lo, lo);
+        }
+      }
+      continue;
+    }
+    if (kind == DAGG_SUM_REAL) {
+      double d = __longlong_as_double((long long)lo);
+      for (int off = 32; off > 0; off >>= 1) {
+        c += (unsigned long long)__shfl_down((long long)c, off, 64);
+        d += __shfl_down(d, off, 64);
+      }
+      if ((threadIdx.x & 63u) == 0) {
+        if (c) atomicAdd(&simple_acc[a].cnt, c);
+        if (d != 0.0) atomicAdd((double *)&simple_acc[a].sum_lo, d);
+      }
+      continue;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      c += (unsigned long long)__shfl_down((long long)c, off, 64);
+      unsigned long long plo = (unsigned long long)__shfl_down((long long)lo, off, 64);
+      long long phi = __shfl_down(hi, off, 64);
+      unsigned long long nlo = lo + plo;
+      hi += phi + (nlo < lo ? 1 : 0);
+      lo = nlo;
+    }
+    if ((threadIdx.x & 63u) == 0) {
+      if (c) atomicAdd(&simple_acc[a].cnt, c);
+      if (lo | (unsigned long long)hi) {
+        __int128 part = (__int128)(
+            ((unsigned __int128)(unsigned long long)hi << 64) | lo);
+        if (plan.simple_ext)
+          atomic_add_i256(&simple_acc[a].sum_lo, &simple_acc[a].sum_hi,
+                          plan.simple_ext + a * 2, part);
+        else {
+          unsigned long long old = atomicAdd(&simple_acc[a].sum_lo, lo);
+          long long carry = (old + lo < old) ? 1 : 0;
+          long long hi_add = hi + carry;
+          if (hi_add)
+            atomicAdd(&simple_acc[a].sum_hi, (unsigned long long)hi_add);
+        }
+      }
+    }
+  }
+}
+
 /* ---------------- fused scan + filter + aggregate ----------------
  * NAGGS is a compile-time bound so all per-row/per-lane state stays in
  * registers. IS_HASH selects grouped aggregation. NLOADS = staged uint4
@@ -1698,73 +1774,7 @@ k_scan_agg(ScanPlan plan,
     }
   }
 
-  if (!IS_HASH) {
-    #pragma unroll
-    for (int a = 0; a < NAGGS; a++) {
-      const int32_t kind = plan.aggs[a].kind;
-      unsigned long long c = l_cnt[a];
-      unsigned long long lo = l_lo[a];
-      long long hi = l_hi[a];
-      if (d_is_fold(kind)) {
-        for (int off = 32; off > 0; off >>= 1) {
-          c += (unsigned long long)__shfl_down((long long)c, off, 64);
-          unsigned long long plo =
-              (unsigned long long)__shfl_down((long long)lo, off, 64);
-          if (d_is_xor(kind)) lo ^= plo;
-          else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT || kind == DAGG_MAX_REAL || kind == DAGG_MIN_REAL)
-            lo = lo > plo ? lo : plo;
-          else lo |= plo;
-        }
-        if ((threadIdx.x & 63u) == 0) {
-          if (c) atomicAdd(&simple_acc[a].cnt, c);
-          if (lo) {
-            if (d_is_xor(kind)) atomicXor(&simple_acc[a].sum_lo, lo);
-            else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT || kind == DAGG_MAX_REAL || kind == DAGG_MIN_REAL)
-              atomicMax(&simple_acc[a].sum_lo, lo);
-            else atomicOr(&simple_acc[a].sum_lo, lo);
-          }
-        }
-        continue;
-      }
-      if (kind == DAGG_SUM_REAL) {
-        double d = __longlong_as_double((long long)lo);
-        for (int off = 32; off > 0; off >>= 1) {
-          c += (unsigned long long)__shfl_down((long long)c, off, 64);
-          d += __shfl_down(d, off, 64);
-        }
-        if ((threadIdx.x & 63u) == 0) {
-          if (c) atomicAdd(&simple_acc[a].cnt, c);
-          if (d != 0.0) atomicAdd((double *)&simple_acc[a].sum_lo, d);
-        }
-        continue;
-      }
-      for (int off = 32; off > 0; off >>= 1) {
-        c += (unsigned long long)__shfl_down((long long)c, off, 64);
-        unsigned long long plo = (unsigned long long)__shfl_down((long long)lo, off, 64);
-        long long phi = __shfl_down(hi, off, 64);
-        unsigned long long nlo = lo + plo;
-        hi += phi + (nlo < lo ? 1 : 0);
-        lo = nlo;
-      }
-      if ((threadIdx.x & 63u) == 0) {
-        if (c) atomicAdd(&simple_acc[a].cnt, c);
-        if (lo | (unsigned long long)hi) {
-          __int128 part = (__int128)(
-              ((unsigned __int128)(unsigned long long)hi << 64) | lo);
-          if (plan.simple_ext)
-            atomic_add_i256(&simple_acc[a].sum_lo, &simple_acc[a].sum_hi,
-                            plan.simple_ext + a * 2, part);
-          else {
-            unsigned long long old = atomicAdd(&simple_acc[a].sum_lo, lo);
-            long long carry = (old + lo < old) ? 1 : 0;
-            long long hi_add = hi + carry;
-            if (hi_add)
-              atomicAdd(&simple_acc[a].sum_hi, (unsigned long long)hi_add);
-          }
-        }
-      }
-    }
-  }
+  if (!IS_HASH) d_simple_epilogue<NAGGS>(plan, simple_acc, l_cnt, l_lo, l_hi);
   if (any_parse_err) {
     if (IS_HASH) atomicOr(ht.error + 1, 1u);
     else atomicOr((unsigned int *)&simple_acc[COPR_MAX_AGGS].cnt, 1u);
@@ -2469,73 +2479,7 @@ k_scan_agg_pipe(ScanPlan plan,
     }
   }
 
-  if (!IS_HASH) {
-    #pragma unroll
-    for (int a = 0; a < NAGGS; a++) {
-      const int32_t kind = plan.aggs[a].kind;
-      unsigned long long c = l_cnt[a];
-      unsigned long long lo = l_lo[a];
-      long long hi = l_hi[a];
-      if (d_is_fold(kind)) {
-        for (int off = 32; off > 0; off >>= 1) {
-          c += (unsigned long long)__shfl_down((long long)c, off, 64);
-          unsigned long long plo =
-              (unsigned long long)__shfl_down((long long)lo, off, 64);
-          if (d_is_xor(kind)) lo ^= plo;
-          else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT || kind == DAGG_MAX_REAL || kind == DAGG_MIN_REAL)
-            lo = lo > plo ? lo : plo;
-          else lo |= plo;
-        }
-        if ((threadIdx.x & 63u) == 0) {
-          if (c) atomicAdd(&simple_acc[a].cnt, c);
-          if (lo) {
-            if (d_is_xor(kind)) atomicXor(&simple_acc[a].sum_lo, lo);
-            else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT || kind == DAGG_MAX_REAL || kind == DAGG_MIN_REAL)
-              atomicMax(&simple_acc[a].sum_lo, lo);
-            else atomicOr(&simple_acc[a].sum_lo, lo);
-          }
-        }
-        continue;
-      }
-      if (kind == DAGG_SUM_REAL) {
-        double d = __longlong_as_double((long long)lo);
-        for (int off = 32; off > 0; off >>= 1) {
-          c += (unsigned long long)__shfl_down((long long)c, off, 64);
-          d += __shfl_down(d, off, 64);
-        }
-        if ((threadIdx.x & 63u) == 0) {
-          if (c) atomicAdd(&simple_acc[a].cnt, c);
-          if (d != 0.0) atomicAdd((double *)&simple_acc[a].sum_lo, d);
-        }
-        continue;
-      }
-      for (int off = 32; off > 0; off >>= 1) {
-        c += (unsigned long long)__shfl_down((long long)c, off, 64);
-        unsigned long long plo = (unsigned long long)__shfl_down((long long)lo, off, 64);
-        long long phi = __shfl_down(hi, off, 64);
-        unsigned long long nlo = lo + plo;
-        hi += phi + (nlo < lo ? 1 : 0);
-        lo = nlo;
-      }
-      if ((threadIdx.x & 63u) == 0) {
-        if (c) atomicAdd(&simple_acc[a].cnt, c);
-        if (lo | (unsigned long long)hi) {
-          __int128 part = (__int128)(
-              ((unsigned __int128)(unsigned long long)hi << 64) | lo);
-          if (plan.simple_ext)
-            atomic_add_i256(&simple_acc[a].sum_lo, &simple_acc[a].sum_hi,
-                            plan.simple_ext + a * 2, part);
-          else {
-            unsigned long long old = atomicAdd(&simple_acc[a].sum_lo, lo);
-            long long carry = (old + lo < old) ? 1 : 0;
-            long long hi_add = hi + carry;
-            if (hi_add)
-              atomicAdd(&simple_acc[a].sum_hi, (unsigned long long)hi_add);
-          }
-        }
-      }
-    }
-  }
+  if (!IS_HASH) d_simple_epilogue<NAGGS>(plan, simple_acc, l_cnt, l_lo, l_hi);
   if (any_parse_err) {
     if (IS_HASH) atomicOr(ht.error + 1, 1u);
     else atomicOr((unsigned int *)&simple_acc[COPR_MAX_AGGS].cnt, 1u);
@@ -2849,6 +2793,458 @@ int dev_celldir_build(DevRegion &rgn, hipStream_t s) {
   e = hipStreamSynchronize(s);
   if (e != hipSuccess) { hipFree(rgn.d_celldir); rgn.d_celldir = nullptr; }
   return 0;
+}
+
+/* ---------------- decoded column planes ----------------
+ * A filter/count request decides each row from ~7 of the ~126 bytes the scan
+ * kernels stage. A plane keeps, per (region, column), the decoded i64 value
+ * and a state byte for every row, so simple aggregates over int/real columns
+ * read 9 bytes per row per column instead of the whole row. */
+
+/* Locate column col_id's cell in one row exactly as the scan kernels do.
+ * dir8 is the row's cell-directory byte for the column (0xFE when the region
+ * has no directory): a hit inspects the target cell alone, 0xFF is absent,
+ * 0xFE walks the row and stops at the column. Reads global memory
+ * (next_cell takes generic pointers, as in k_scan_fc_direct). */
+enum { LOC_ABSENT = 0, LOC_CELL, LOC_ERR, LOC_V2 };
+__device__ static inline int d_col_locate(const uint8_t *vp, uint32_t vlen,
+                                          uint32_t dir8, int64_t col_id,
+                                          CellView *cell) {
+  if (vlen == 0 || (vlen == 1 && vp[0] == 0)) return LOC_ABSENT;
+  if (vp[0] == 128) return LOC_V2;
+  int64_t cid;
+  uint32_t coff;
+  /* next_cell's word path leaves these untouched */
+  cell->has_real = false;
+  cell->has_dec = false;
+  cell->dwide = nullptr;
+  cell->ival = 0;
+  if (dir8 == 0xFFu) return LOC_ABSENT;
+  if (dir8 < 0xFEu) {
+    uint32_t pos = dir8;
+    if (next_cell(vp, vlen, &pos, &cid, &coff, cell) && cid == col_id)
+      return LOC_CELL;
+    return LOC_ERR;
+  }
+  uint32_t pos = 0;
+  while (pos < vlen) {
+    if (!next_cell(vp, vlen, &pos, &cid, &coff, cell)) return LOC_ERR;
+    if (cid == col_id) return LOC_CELL;
+  }
+  return LOC_ABSENT;
+}
+
+/* One-time pass per (region, column): classify every row's cell and store
+ * the decoded value. n_rowparse counts the rows left to query time. */
+__global__ void __launch_bounds__(256)
+k_build_colplane(const uint8_t *__restrict__ vals,
+                 const uint64_t *__restrict__ val_offs, uint64_t n_rows,
+                 const uint8_t *__restrict__ dirp, int64_t col_id,
+                 int64_t *__restrict__ pval, uint8_t *__restrict__ pst,
+                 unsigned long long *__restrict__ n_rowparse) {
+  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  unsigned long long rp = 0;
+  for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       row < n_rows; row += stride) {
+    uint64_t o0 = val_offs[row], o1 = val_offs[row + 1];
+    uint32_t dir8 = dirp ? (uint32_t)dirp[row] : 0xFEu;
+    CellView cell;
+    int64_t v = 0;
+    uint8_t st;
+    switch (d_col_locate(vals + o0, (uint32_t)(o1 - o0), dir8, col_id, &cell)) {
+      case LOC_ABSENT: st = PST_ABSENT; break;
+      case LOC_ERR:    st = PST_ERR; break;
+      case LOC_V2:     st = PST_ROWPARSE; break;
+      default:
+        if (cell.is_null) st = PST_NULL;
+        else if (cell.has_int) { st = PST_INT; v = cell.ival; }
+        else if (cell.has_real) { st = PST_REAL; v = cell.ival; }
+        else st = PST_ROWPARSE;
+        break;
+    }
+    pval[row] = v;
+    pst[row] = st;
+    rp += st == PST_ROWPARSE ? 1ull : 0ull;
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    rp += (unsigned long long)__shfl_down((long long)rp, off, 64);
+  if ((threadIdx.x & 63u) == 0 && rp) atomicAdd(n_rowparse, rp);
+}
+
+void dev_colplane_free(DevRegion &rgn) {
+  for (int32_t i = 0; i < rgn.n_planes; i++) {
+    hipFree(rgn.planes[i].val);
+    hipFree(rgn.planes[i].st);
+    rgn.planes[i] = DevRegion::ColPlane{};
+  }
+  rgn.n_planes = 0;
+  rgn.plane_bytes = 0;
+}
+
+const DevRegion::ColPlane *dev_colplane_get(DevRegion &rgn, int64_t col_id,
+                                            uint64_t budget_bytes,
+                                            hipStream_t s, uint64_t *built) {
+  for (int32_t i = 0; i < rgn.n_planes; i++)
+    if (rgn.planes[i].col_id == col_id)
+      return rgn.planes[i].val ? &rgn.planes[i] : nullptr;
+  if (!rgn.n_kv || rgn.n_planes == COPR_MAX_PLANES) return nullptr;
+  const uint64_t cost = rgn.n_kv * 9;
+  if (rgn.plane_bytes + cost > budget_bytes) return nullptr;
+  DevRegion::ColPlane p{};
+  p.col_id = col_id;
+  unsigned long long *d_rp = nullptr;
+  unsigned long long h_rp = 0;
+  /* tail slack like the directory's: the plane kernel's 16 B loads round
+     the last pair up */
+  hipError_t e = hipMalloc((void **)&p.val, rgn.n_kv * 8 + 2048);
+  if (e == hipSuccess) e = hipMalloc((void **)&p.st, rgn.n_kv + 2048);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_rp, 8);
+  if (e == hipSuccess) e = hipMemsetAsync(d_rp, 0, 8, s);
+  if (e == hipSuccess) {
+    const uint8_t *dirp =
+        (rgn.d_celldir && col_id >= 1 && col_id <= 16)
+            ? rgn.d_celldir + (uint64_t)(col_id - 1) * rgn.n_kv : nullptr;
+    uint32_t grid = (uint32_t)min((rgn.n_kv + 255) / 256, (uint64_t)16384);
+    hipLaunchKernelGGL(k_build_colplane, dim3(grid), dim3(256), 0, s,
+                       rgn.d_vals, rgn.d_val_offs, rgn.n_kv, dirp, col_id,
+                       p.val, p.st, d_rp);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(&h_rp, d_rp, 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  hipFree(d_rp);
+  if (e != hipSuccess) {             /* optional, like the directory */
+    (void)hipGetLastError();
+    hipFree(p.val);
+    hipFree(p.st);
+    return nullptr;
+  }
+  DevRegion::ColPlane &slot = rgn.planes[rgn.n_planes++];
+  if (h_rp * 8 > rgn.n_kv) {
+    /* mostly rows that need the row bytes anyway (row-v2 region, decimal or
+       bytes column): the scan path reads less. Remember the verdict. */
+    hipFree(p.val);
+    hipFree(p.st);
+    slot = DevRegion::ColPlane{};
+    slot.col_id = col_id;
+    return nullptr;
+  }
+  p.n_rowparse = h_rp;
+  slot = p;
+  rgn.plane_bytes += cost;
+  if (built) (*built)++;
+  return &slot;
+}
+
+/* One plane channel for one row -> what the scan kernels' collect step
+ * produces for the column: value + CH_* flags. want: 0 int filter, 1 real
+ * filter, 2 int-valued aggregate (sum/max/min), 3 count(col). */
+enum { CH_FOUND = 1, CH_NULL = 2, CH_ERR = 4 };
+struct ChanRes { int64_t v; uint32_t fl; };
+
+/* ROWPARSE rows: resolve the column from the row bytes with the request's
+ * signedness / type. Rare, so kept out of line to leave the streaming loop
+ * small. */
+__device__ __noinline__ static ChanRes d_plane_resolve(
+    const uint8_t *dirp, uint64_t row, int64_t col_id, bool uns, int want,
+    const uint8_t *vals, const uint64_t *val_offs) {
+  ChanRes cr{0, 0};
+  uint64_t o0 = val_offs[row], o1 = val_offs[row + 1];
+  const uint8_t *vp = vals + o0;
+  uint32_t vlen = (uint32_t)(o1 - o0);
+  uint32_t dir8 = dirp ? (uint32_t)dirp[row] : 0xFEu;
+  CellView cell;
+  int loc = d_col_locate(vp, vlen, dir8, col_id, &cell);
+  if (loc == LOC_ERR) {
+    cr.fl = CH_ERR;
+  } else if (loc == LOC_V2) {
+    V2Row r;
+    uint32_t s, e;
+    if (!d_v2_parse(vp, vlen, &r)) { cr.fl = CH_ERR; return cr; }
+    int fs = d_v2_find(r, col_id, &s, &e);
+    if (fs < 0) return cr;
+    cr.fl = CH_FOUND;
+    if (fs == 0) { cr.fl |= CH_NULL; return cr; }
+    if (want == 1) {
+      if (e - s != 8) { cr.fl |= CH_ERR; return cr; }
+      uint64_t u = d_be_u64(r.vals + s);
+      cr.v = (int64_t)((u & 0x8000000000000000ull)
+                           ? (u ^ 0x8000000000000000ull) : ~u);
+    } else if (want != 3) {
+      if (!d_v2_int(r.vals + s, e - s, uns, &cr.v)) cr.fl |= CH_ERR;
+    }
+  } else if (loc == LOC_CELL) {
+    cr.fl = CH_FOUND;
+    if (want <= 1) {
+      if (cell.is_null) cr.fl |= CH_NULL;
+      else if (want == 1 ? cell.has_real : cell.has_int) cr.v = cell.ival;
+      else cr.fl |= CH_ERR;
+    } else {
+      if (cell.is_null) cr.fl |= CH_NULL;
+      cr.v = cell.ival;
+      if (!cell.is_null && !cell.has_int && !cell.has_real &&
+          !cell.has_dec && !cell.dwide)
+        cr.fl |= CH_ERR;
+    }
+  }
+  return cr;
+}
+
+__device__ static inline ChanRes d_plane_chan(
+    const PlaneRef &pr, uint32_t st, int64_t pv, uint64_t row, int64_t col_id,
+    bool uns, int want, const uint8_t *vals, const uint64_t *val_offs) {
+  switch (st) {
+    case PST_INT:    return ChanRes{pv, want == 1 ? (uint32_t)(CH_FOUND | CH_ERR)
+                                                  : (uint32_t)CH_FOUND};
+    case PST_REAL:   return ChanRes{pv, want == 0 ? (uint32_t)(CH_FOUND | CH_ERR)
+                                                  : (uint32_t)CH_FOUND};
+    case PST_NULL:   return ChanRes{0, CH_FOUND | CH_NULL};
+    case PST_ABSENT: return ChanRes{0, 0};
+    case PST_ERR:    return ChanRes{0, CH_ERR};
+    default:
+      return d_plane_resolve(pr.dir, row, col_id, uns, want, vals, val_offs);
+  }
+}
+
+/* Simple aggregates over column planes: no LDS staging; each lane loads 16 B
+ * of every referenced value plane (two rows) plus the two state bytes, UNR
+ * pairs in flight, grid-stride. The keep decision and the accumulate rules
+ * are the scan kernels' (d_filter_keep / d_filter2_keep, per-lane i128
+ * partials, d_simple_epilogue), so accumulator layout, overflow behaviour and
+ * the parse-error flag are unchanged. */
+template <int NAGGS, int UNR>
+__global__ void __launch_bounds__(256)
+k_plane_agg(ScanPlan plan, PlaneSet ps,
+            const uint8_t *__restrict__ vals,
+            const uint64_t *__restrict__ val_offs, uint64_t n_rows,
+            SimpleAggAcc *__restrict__ simple_acc) {
+  unsigned long long l_cnt[NAGGS];
+  unsigned long long l_lo[NAGGS];
+  long long l_hi[NAGGS];
+  #pragma unroll
+  for (int a = 0; a < NAGGS; a++) { l_cnt[a] = 0; l_lo[a] = 0; l_hi[a] = 0; }
+  bool any_parse_err = false;
+
+  const uint64_t n_pairs = (n_rows + 1) >> 1;
+  const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * 256u * UNR + threadIdx.x;
+       p0 < n_pairs; p0 += step) {
+    /* all loads first (clamped, unconditional per channel), then the rows */
+    longlong2 fv[UNR], f2v[UNR], av[NAGGS][UNR];
+    uint16_t fs[UNR], f2s[UNR], ast[NAGGS][UNR];
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = min(p0 + (uint64_t)u * 256u, n_pairs - 1);
+      fv[u] = make_longlong2(0, 0); fs[u] = 0;
+      f2v[u] = make_longlong2(0, 0); f2s[u] = 0;
+      if (ps.f.val) {
+        fv[u] = ((const longlong2 *)ps.f.val)[p];
+        fs[u] = ((const uint16_t *)ps.f.st)[p];
+      }
+      if (ps.f2.val) {
+        f2v[u] = ((const longlong2 *)ps.f2.val)[p];
+        f2s[u] = ((const uint16_t *)ps.f2.st)[p];
+      }
+      #pragma unroll
+      for (int a = 0; a < NAGGS; a++) {
+        av[a][u] = make_longlong2(0, 0); ast[a][u] = 0;
+        if (ps.a[a].val) {
+          av[a][u] = ((const longlong2 *)ps.a[a].val)[p];
+          ast[a][u] = ((const uint16_t *)ps.a[a].st)[p];
+        }
+      }
+    }
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = p0 + (uint64_t)u * 256u;
+      #pragma unroll
+      for (int h = 0; h < 2; h++) {
+        uint64_t row = p * 2 + h;
+        if (p >= n_pairs || row >= n_rows) continue;
+        ChanRes f{0, 0}, f2{0, 0}, ag[NAGGS];
+        if (ps.f.val)
+          f = d_plane_chan(ps.f, (fs[u] >> (8 * h)) & 0xFFu,
+                           h ? fv[u].y : fv[u].x, row, plan.filter_col_id,
+                           plan.filter_col_unsigned != 0,
+                           plan.filter_is_real ? 1 : 0, vals, val_offs);
+        if (ps.f2.val)
+          f2 = d_plane_chan(ps.f2, (f2s[u] >> (8 * h)) & 0xFFu,
+                            h ? f2v[u].y : f2v[u].x, row, plan.filter2_col_id,
+                            plan.filter2_col_unsigned != 0,
+                            plan.filter2_is_real ? 1 : 0, vals, val_offs);
+        uint32_t fl_or = f.fl | f2.fl;
+        #pragma unroll
+        for (int a = 0; a < NAGGS; a++) {
+          ag[a] = ChanRes{0, 0};
+          if (ps.a[a].val)
+            ag[a] = d_plane_chan(ps.a[a], (ast[a][u] >> (8 * h)) & 0xFFu,
+                                 h ? av[a][u].y : av[a][u].x, row,
+                                 plan.aggs[a].col_id,
+                                 plan.aggs[a].col_unsigned != 0,
+                                 plan.aggs[a].kind == DAGG_COUNT_COL ? 3 : 2,
+                                 vals, val_offs);
+          fl_or |= ag[a].fl;
+        }
+        /* a parse error on any referenced column fails the request whether
+           or not the filter keeps the row, as in the scan kernels */
+        if (fl_or & CH_ERR) { any_parse_err = true; continue; }
+        if (!(d_filter_keep(plan, (f.fl & CH_FOUND) != 0,
+                            (f.fl & CH_NULL) != 0, f.v) &&
+              d_filter2_keep(plan, (f2.fl & CH_FOUND) != 0,
+                             (f2.fl & CH_NULL) != 0, f2.v)))
+          continue;
+        #pragma unroll
+        for (int a = 0; a < NAGGS; a++) {
+          const int32_t kind = plan.aggs[a].kind;
+          if (kind == DAGG_COUNT_ROWS) { l_cnt[a]++; continue; }
+          if ((ag[a].fl & (CH_FOUND | CH_NULL)) != CH_FOUND) continue;
+          l_cnt[a]++;
+          const int64_t v = ag[a].v;
+          if (kind == DAGG_SUM_INT) {
+            unsigned long long old = l_lo[a];
+            unsigned long long nv = old + (unsigned long long)v;
+            l_hi[a] += (nv < old ? 1 : 0) + (v < 0 ? -1 : 0);
+            l_lo[a] = nv;
+          } else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT) {
+            unsigned long long b =
+                d_fold_xform(kind, v, plan.aggs[a].col_unsigned);
+            l_lo[a] = l_lo[a] > b ? l_lo[a] : b;
+          }
+        }
+      }
+    }
+  }
+
+  d_simple_epilogue<NAGGS>(plan, simple_acc, l_cnt, l_lo, l_hi);
+  if (any_parse_err)
+    atomicOr((unsigned int *)&simple_acc[COPR_MAX_AGGS].cnt, 1u);
+}
+
+/* k_plane_agg specialised for one same-signedness int filter + count(*) over
+ * a plane without ROWPARSE rows — the cfg2 shape, as FASTFC is to the pipe
+ * kernel. The generic kernel spends ~100 instructions per row on the
+ * plan-driven compare and runs issue-bound; here the host folds comparer,
+ * signedness and constant into one biased unsigned range test
+ *   keep = (((v ^ bias) - lo) <= span) != invert
+ * so the row loop is a handful of VALU ops and the kernel follows the
+ * loads. Same results: NULL never keeps, ABSENT takes the request's default
+ * fill (keep_absent, decided on the host with the same test), REAL and ERR
+ * cells raise the parse-error flag. */
+struct PlaneFcArgs {
+  unsigned long long bias, lo, span;
+  uint32_t invert, keep_absent;
+};
+
+__global__ void __launch_bounds__(256)
+k_plane_fc(PlaneFcArgs fa, const longlong2 *__restrict__ val,
+           const uint16_t *__restrict__ st, uint64_t n_rows,
+           SimpleAggAcc *__restrict__ simple_acc) {
+  constexpr int UNR = 4;
+  unsigned long long cnt = 0;
+  uint32_t bad = 0;
+  const uint64_t n_pairs = (n_rows + 1) >> 1;
+  const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * 256u * UNR + threadIdx.x;
+       p0 < n_pairs; p0 += step) {
+    longlong2 v[UNR];
+    uint32_t s[UNR];
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = min(p0 + (uint64_t)u * 256u, n_pairs - 1);
+      v[u] = val[p];
+      s[u] = st[p];
+    }
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = p0 + (uint64_t)u * 256u;
+      #pragma unroll
+      for (int h = 0; h < 2; h++) {
+        bool live = p < n_pairs && p * 2 + h < n_rows;
+        uint32_t sb = (s[u] >> (8 * h)) & 0xFFu;
+        unsigned long long key =
+            (unsigned long long)(h ? v[u].y : v[u].x) ^ fa.bias;
+        bool k_int = ((key - fa.lo) <= fa.span) != (fa.invert != 0);
+        bool keep = sb == PST_INT ? k_int
+                                  : (sb == PST_ABSENT && fa.keep_absent != 0);
+        cnt += (live && keep) ? 1ull : 0ull;
+        bad |= (live && (sb == PST_REAL || sb >= PST_ROWPARSE)) ? 1u : 0u;
+      }
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    cnt += (unsigned long long)__shfl_down((long long)cnt, off, 64);
+  if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(&simple_acc[0].cnt, cnt);
+  if (bad) atomicOr((unsigned int *)&simple_acc[COPR_MAX_AGGS].cnt, 1u);
+}
+
+/* fold the plan's filter into k_plane_fc's range test; false = the plan or
+   the plane does not fit the specialisation */
+static bool plane_fc_args(const ScanPlan &plan, const PlaneSet &ps,
+                          PlaneFcArgs *fa) {
+  if (plan.n_aggs != 1 || plan.aggs[0].kind != DAGG_COUNT_ROWS ||
+      !plan.has_filter || !ps.f.val || ps.f2.val || plan.filter2_on ||
+      plan.filter_is_real || plan.filter_decode_only ||
+      (plan.filter_col_unsigned != 0) != (plan.filter_const_unsigned != 0) ||
+      ps.f.n_rowparse)
+    return false;
+  const unsigned long long MAXU = ~0ull;
+  fa->bias = plan.filter_col_unsigned ? 0ull : 0x8000000000000000ull;
+  const unsigned long long c =
+      (unsigned long long)plan.filter_const ^ fa->bias;
+  bool empty = false;
+  fa->invert = 0;
+  switch (plan.filter_cmp) {
+    case CMP_LT: empty = c == 0; fa->lo = 0; fa->span = c - 1; break;
+    case CMP_LE: fa->lo = 0; fa->span = c; break;
+    case CMP_GT: empty = c == MAXU; fa->lo = c + 1; fa->span = MAXU - (c + 1); break;
+    case CMP_GE: fa->lo = c; fa->span = MAXU - c; break;
+    case CMP_EQ: fa->lo = c; fa->span = 0; break;
+    default:     fa->lo = c; fa->span = 0; fa->invert = 1; break;   /* NE */
+  }
+  if (empty || plan.filter_const_null) {   /* never true: all-range, inverted */
+    fa->lo = 0; fa->span = MAXU; fa->invert = 1;
+  }
+  unsigned long long mk =
+      (unsigned long long)plan.filter_missing_val ^ fa->bias;
+  fa->keep_absent = (!plan.filter_missing_null &&
+                     (((mk - fa->lo) <= fa->span) != (fa->invert != 0)))
+                        ? 1u : 0u;
+  return true;
+}
+
+int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
+                         const DevRegion &rgn, SimpleAggAcc *d_simple,
+                         void *stream) {
+  if (!rgn.n_kv) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t n_pairs = (rgn.n_kv + 1) >> 1;
+  PlaneFcArgs fa;
+  if (plane_fc_args(plan, ps, &fa)) {
+    uint64_t nb = (n_pairs + 256u * 4 - 1) / (256u * 4);
+    uint32_t grid = (uint32_t)(nb < 4096 ? nb : 4096);
+    hipLaunchKernelGGL(k_plane_fc, dim3(grid), dim3(256), 0, s, fa,
+                       (const longlong2 *)ps.f.val,
+                       (const uint16_t *)ps.f.st, rgn.n_kv, d_simple);
+    return (int)hipGetLastError();
+  }
+  #define CASE(N, U)                                                         \
+    {                                                                        \
+      uint64_t nb = (n_pairs + 256u * U - 1) / (256u * U);                   \
+      uint32_t grid = (uint32_t)(nb < 2048 ? nb : 2048);                     \
+      hipLaunchKernelGGL((k_plane_agg<N, U>), dim3(grid), dim3(256), 0, s,   \
+                         plan, ps, rgn.d_vals, rgn.d_val_offs, rgn.n_kv,     \
+                         d_simple);                                          \
+    }
+  switch (plan.n_aggs) {
+    case 1: CASE(1, 4); break;
+    case 2: CASE(2, 2); break;
+    case 3: CASE(3, 2); break;
+    case 4: CASE(4, 2); break;
+    default: CASE(COPR_MAX_AGGS, 1); break;
+  }
+  #undef CASE
+  return (int)hipGetLastError();
 }
 
 /* ---------------- loader-wave ring pipeline (filter+count) ----------------

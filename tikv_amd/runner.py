@@ -540,6 +540,12 @@ class Engine:
                                (st, self._lib.copr_last_error().decode()))
         return cs.value, kvs.value, byts.value
 
+    def plane_stats(self):
+        """(launches, builds): per-region kernel launches that read decoded
+        column planes, and planes built, since the engine was created."""
+        return (self._lib.copr_engine_plane_launches(self._h),
+                self._lib.copr_engine_plane_builds(self._h))
+
     def close(self):
         if self._h:
             self._lib.copr_engine_destroy(self._h)
