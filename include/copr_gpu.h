@@ -99,6 +99,11 @@ void        copr_result_free(CoprSelectResult *);
  * the row bytes, and how many planes it has built. Monotonic. */
 uint64_t    copr_engine_plane_launches(const copr_engine *);
 uint64_t    copr_engine_plane_builds(const copr_engine *);
+/* Hash aggregation over column planes: launches of the plane
+ * hash kernel, one per region per attempt (a grown table retries). Counted
+ * apart: copr_engine_plane_launches stays the simple-aggregate count, while
+ * copr_engine_plane_builds counts every build whichever consumer asked. */
+uint64_t    copr_engine_hash_plane_launches(const copr_engine *);
 
 /* ---- checksum (REQ_TYPE_CHECKSUM = 105; src/coprocessor/checksum.rs:59-114) ----
  * CRC-64/XZ per KV over key||value, XOR-folded (order-independent). */

@@ -87,6 +87,10 @@ extern "C" uint64_t copr_engine_plane_builds(const copr_engine *eng) {
   return eng ? eng->plane_builds : 0;
 }
 
+extern "C" uint64_t copr_engine_hash_plane_launches(const copr_engine *eng) {
+  return eng ? eng->hash_plane_launches : 0;
+}
+
 /* ---------------- region ---------------- */
 extern "C" copr_status copr_region_create(copr_engine *eng,
                                           const uint8_t *keys, const uint64_t *key_offs,
@@ -998,8 +1002,29 @@ static bool plane_plan_ok(const ScanPlan &sp) {
   return any_col;
 }
 
+/* FastHashAgg (int group key) over a table scan with the same
+   keep decision, and aggregates that need a column's int or <= 38-digit
+   decimal value or its presence. count(NULL) rides a column id that never
+   exists and has nothing to read from a plane. */
+static bool hash_plane_plan_ok(const ScanPlan &sp) {
+  if (sp.mode != 2 || sp.index_mode || sp.rpn_on || sp.n_xcap ||
+      sp.filter_decode_only || sp.dec2_col_id || sp.group_col_id <= 0)
+    return false;
+  for (int a = 0; a < sp.n_aggs; a++) {
+    switch (sp.aggs[a].kind) {
+      case DAGG_COUNT_ROWS: break;
+      case DAGG_COUNT_COL: case DAGG_SUM_INT: case DAGG_SUM_DEC:
+      case DAGG_MAX_INT: case DAGG_MIN_INT:
+        if (sp.aggs[a].col_id <= 0) return false;
+        break;
+      default: return false;
+    }
+  }
+  return true;
+}
+
 static bool plane_set_used(const PlaneSet &ps) {
-  if (ps.f.val || ps.f2.val) return true;
+  if (ps.g.val || ps.f.val || ps.f2.val) return true;
   for (int a = 0; a < COPR_MAX_AGGS; a++)
     if (ps.a[a].val) return true;
   return false;
@@ -1011,17 +1036,21 @@ static bool plane_set_used(const PlaneSet &ps) {
    path sees it, and that depends on how the scan locates cells: through the
    directory when every referenced id has a directory plane (1..16), by
    walking otherwise. So with a directory present the same id rule as
-   wire_celldir applies. */
+   wire_celldir applies.
+   hash = the k_plane_hash consumer: it also wires the group column, reads
+   decimal rows from the plane, and may spend the region's full value bytes
+   on planes where the simple consumer stops at half. */
 static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
-                       PlaneSet *ps) {
+                       PlaneSet *ps, bool hash = false) {
   *ps = PlaneSet{};
   if (!dev.n_kv) return false;
-  uint64_t budget = dev.val_bytes / 2;
+  uint64_t budget = hash ? dev.val_bytes : dev.val_bytes / 2;
   if (const char *e = getenv("COPR_PLANE_BUDGET_MB"))
     budget = (uint64_t)strtoull(e, nullptr, 10) << 20;
   struct Want { int64_t col; PlaneRef *ref; };
-  Want want[COPR_MAX_AGGS + 2];
+  Want want[COPR_MAX_AGGS + 3];
   int n_want = 0;
+  if (hash) want[n_want++] = {sp.group_col_id, &ps->g};
   if (sp.has_filter) want[n_want++] = {sp.filter_col_id, &ps->f};
   if (sp.filter2_on) want[n_want++] = {sp.filter2_col_id, &ps->f2};
   for (int a = 0; a < sp.n_aggs; a++)
@@ -1034,12 +1063,30 @@ static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
     const DevRegion::ColPlane *p = dev_colplane_get(
         dev, want[i].col, budget, eng->stream, &eng->plane_builds);
     if (!p) return false;
+    /* k_plane_agg / k_plane_fc take a decimal row for a ROWPARSE row, so a
+       mostly-decimal plane is as useless to them as a tombstoned one */
+    const uint64_t n_rp = hash ? p->n_rowparse : p->n_rowparse + p->n_dec;
+    if (!hash && n_rp * 8 > dev.n_kv) return false;
     want[i].ref->val = p->val;
     want[i].ref->st = p->st;
-    want[i].ref->n_rowparse = p->n_rowparse;
+    want[i].ref->n_rowparse = n_rp;
     want[i].ref->dir =
         dev.d_celldir ? dev.d_celldir + (uint64_t)(want[i].col - 1) * dev.n_kv
                       : nullptr;
+  }
+  if (hash) {
+    /* a column referenced twice is loaded once (cfg3 groups by and averages
+       the same column) */
+    for (int a = 0; a < sp.n_aggs; a++) {
+      const PlaneRef &r = ps->a[a];
+      if (!r.val) continue;
+      if (r.val == ps->g.val) ps->a_src[a] = 1;
+      else if (r.val == ps->f.val) ps->a_src[a] = 2;
+      else if (r.val == ps->f2.val) ps->a_src[a] = 3;
+      else
+        for (int b = 0; b < a; b++)
+          if (ps->a[b].val == r.val) { ps->a_src[a] = 4 + b; break; }
+    }
   }
   return true;
 }
@@ -2367,6 +2414,17 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         c = HashAggTable{};
         eng->ht_cache_tsize = 0;
       };
+      /* column planes: decided per region, all or nothing; a
+         missing plane is built here, before the first attempt's timed
+         events, and retries after a table-full reuse the wiring. A region
+         without planes scans into the same table. */
+      std::vector<PlaneSet> psets;
+      if (!getenv("COPR_NO_PLANES") && hash_plane_plan_ok(pl.sp)) {
+        psets.resize(n_regions);
+        for (uint32_t rg = 0; rg < n_regions; rg++)
+          if (!plane_wire(eng, regions[rg]->dev, pl.sp, &psets[rg], true))
+            psets[rg] = PlaneSet{};
+      }
       for (int attempt = 0; attempt < 4; attempt++) {
         /* the table buffers persist on the engine across requests: the
            per-request hipMalloc/hipFree set measured ~3 ms at cfg3 scale */
@@ -2441,6 +2499,17 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             slots /= 2;
             table_b = 16u + slots * (8 + (uint32_t)sp.n_aggs *
                                              (uint32_t)sizeof(SimpleAggAcc));
+          }
+          if (!psets.empty() && plane_set_used(psets[rg])) {
+            /* no row staging: the LDS holds the pre-agg table alone */
+            sp.lds_agg_slots = slots;
+            sp.lds_agg_off = 0;
+            sp.lds_bytes = slots ? table_b - 16u : 0u;
+            int le = dev_plane_hash_launch(sp, psets[rg], regions[rg]->dev,
+                                           ht, eng->stream);
+            eng->hash_plane_launches++;
+            if (le) { free_ht(); return SET_ERR(COPR_ERR_INTERNAL, "plane hash launch failed"); }
+            continue;
           }
           /* hash mode prefers the glds-pipelined kernel (DMA-staged dir
              planes + overlap; r01's single-buffer kernel measured 47%

@@ -37,13 +37,17 @@ struct DevRegion {
      and a state byte for every row, built lazily by the first plane-eligible
      request that references the column and cached until the region is
      destroyed. A slot with val == nullptr is a tombstone: the build found
-     the column unsuited (too many ROWPARSE rows) and is not repeated. */
+     the column unsuited (too many ROWPARSE rows) and is not repeated.
+     Decimal rows do not count towards the tombstone: the hash consumer
+      reads them from the plane; the simple consumer, which treats
+     them as ROWPARSE, declines such a plane per request instead. */
 #define COPR_MAX_PLANES 16
   struct ColPlane {
     int64_t col_id = 0;
     int64_t *val = nullptr;        /* [n_kv] (+ tail slack) */
     uint8_t *st = nullptr;         /* [n_kv] (+ tail slack), PST_* */
     uint64_t n_rowparse = 0;       /* rows left to query time (PST_ROWPARSE) */
+    uint64_t n_dec = 0;            /* rows holding a decimal (PST_DEC0 + frac) */
   };
   ColPlane planes[COPR_MAX_PLANES];
   int32_t n_planes = 0;
@@ -56,6 +60,11 @@ struct DevRegion {
    are neither int, real nor NULL error or count depending on the consumer);
    ERR = locating the column in this row fails, whoever asks. */
 enum { PST_INT = 0, PST_REAL, PST_NULL, PST_ABSENT, PST_ROWPARSE, PST_ERR };
+/* decimal of at most 18 digits: st = PST_DEC0 + frac (frac <= 18), val = the
+   scaled i64. Only k_plane_hash's sum(decimal) channel reads the value; every
+   other consumer treats the state as ROWPARSE. Wide decimals (19..38 digits)
+   stay PST_ROWPARSE. */
+enum { PST_DEC0 = 16 };
 
 /* compare kinds (order matches oracle CmpKind) */
 enum { CMP_LT = 0, CMP_LE, CMP_GT, CMP_GE, CMP_EQ, CMP_NE };
@@ -271,6 +280,11 @@ struct PlaneRef {
 struct PlaneSet {
   PlaneRef f, f2;
   PlaneRef a[COPR_MAX_AGGS];
+  /* k_plane_hash only: the group column, and per aggregate where its plane
+     registers come from, so that a column referenced twice is loaded once:
+     0 own load, 1 group, 2 filter, 3 filter2, 4 + b = aggregate b (b < a) */
+  PlaneRef g;
+  int32_t a_src[COPR_MAX_AGGS];
 };
 
 /* hash-agg table (device): parallel arrays.
@@ -328,6 +342,11 @@ void dev_colplane_free(DevRegion &rgn);
 int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
                          const DevRegion &rgn, SimpleAggAcc *d_simple,
                          void *stream);
+/* int-key hash aggregation (mode 2) over column planes; the
+   plan carries table_size and lds_agg_slots as for dev_scan_launch */
+int dev_plane_hash_launch(const ScanPlan &plan, const PlaneSet &ps,
+                          const DevRegion &rgn, const HashAggTable &ht,
+                          void *stream);
 int dev_stream_agg(const ScanPlan &plan, const DevRegion &rgn, void *stream,
                    std::vector<SimpleAggAcc> *h_accs,
                    std::vector<long long> *h_gk, std::vector<uint8_t> *h_gs);
@@ -407,9 +426,11 @@ struct copr_engine {
      memsets, freed in engine destroy */
   copr::SimpleAggAcc *d_simple_acc = nullptr;
   unsigned long long *d_simple_ext = nullptr;
-  /* diagnostics (copr_engine_plane_launches / _builds) */
+  /* diagnostics (copr_engine_plane_launches / _builds /
+     copr_engine_hash_plane_launches) */
   uint64_t plane_launches = 0;
   uint64_t plane_builds = 0;
+  uint64_t hash_plane_launches = 0;
 };
 
 struct copr_region {

@@ -2841,9 +2841,9 @@ k_build_colplane(const uint8_t *__restrict__ vals,
                  const uint64_t *__restrict__ val_offs, uint64_t n_rows,
                  const uint8_t *__restrict__ dirp, int64_t col_id,
                  int64_t *__restrict__ pval, uint8_t *__restrict__ pst,
-                 unsigned long long *__restrict__ n_rowparse) {
+                 unsigned long long *__restrict__ n_rowparse /* [2]: +dec */) {
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  unsigned long long rp = 0;
+  unsigned long long rp = 0, nd = 0;
   for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
        row < n_rows; row += stride) {
     uint64_t o0 = val_offs[row], o1 = val_offs[row + 1];
@@ -2859,16 +2859,25 @@ k_build_colplane(const uint8_t *__restrict__ vals,
         if (cell.is_null) st = PST_NULL;
         else if (cell.has_int) { st = PST_INT; v = cell.ival; }
         else if (cell.has_real) { st = PST_REAL; v = cell.ival; }
+        else if (cell.has_dec && (uint32_t)cell.dfrac <= 18u) {
+          /* has_dec means prec <= 18, so frac fits beside PST_DEC0 */
+          st = (uint8_t)(PST_DEC0 + cell.dfrac);
+          v = cell.dscaled;
+        }
         else st = PST_ROWPARSE;
         break;
     }
     pval[row] = v;
     pst[row] = st;
     rp += st == PST_ROWPARSE ? 1ull : 0ull;
+    nd += st >= PST_DEC0 ? 1ull : 0ull;
   }
-  for (int off = 32; off > 0; off >>= 1)
+  for (int off = 32; off > 0; off >>= 1) {
     rp += (unsigned long long)__shfl_down((long long)rp, off, 64);
+    nd += (unsigned long long)__shfl_down((long long)nd, off, 64);
+  }
   if ((threadIdx.x & 63u) == 0 && rp) atomicAdd(n_rowparse, rp);
+  if ((threadIdx.x & 63u) == 0 && nd) atomicAdd(n_rowparse + 1, nd);
 }
 
 void dev_colplane_free(DevRegion &rgn) {
@@ -2892,14 +2901,14 @@ const DevRegion::ColPlane *dev_colplane_get(DevRegion &rgn, int64_t col_id,
   if (rgn.plane_bytes + cost > budget_bytes) return nullptr;
   DevRegion::ColPlane p{};
   p.col_id = col_id;
-  unsigned long long *d_rp = nullptr;
-  unsigned long long h_rp = 0;
+  unsigned long long *d_rp = nullptr;   /* [0] ROWPARSE rows, [1] decimal rows */
+  unsigned long long h_rp[2] = {0, 0};
   /* tail slack like the directory's: the plane kernel's 16 B loads round
      the last pair up */
   hipError_t e = hipMalloc((void **)&p.val, rgn.n_kv * 8 + 2048);
   if (e == hipSuccess) e = hipMalloc((void **)&p.st, rgn.n_kv + 2048);
-  if (e == hipSuccess) e = hipMalloc((void **)&d_rp, 8);
-  if (e == hipSuccess) e = hipMemsetAsync(d_rp, 0, 8, s);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_rp, 16);
+  if (e == hipSuccess) e = hipMemsetAsync(d_rp, 0, 16, s);
   if (e == hipSuccess) {
     const uint8_t *dirp =
         (rgn.d_celldir && col_id >= 1 && col_id <= 16)
@@ -2911,7 +2920,7 @@ const DevRegion::ColPlane *dev_colplane_get(DevRegion &rgn, int64_t col_id,
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    e = hipMemcpyAsync(&h_rp, d_rp, 8, hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(h_rp, d_rp, 16, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   hipFree(d_rp);
   if (e != hipSuccess) {             /* optional, like the directory */
@@ -2921,16 +2930,19 @@ const DevRegion::ColPlane *dev_colplane_get(DevRegion &rgn, int64_t col_id,
     return nullptr;
   }
   DevRegion::ColPlane &slot = rgn.planes[rgn.n_planes++];
-  if (h_rp * 8 > rgn.n_kv) {
-    /* mostly rows that need the row bytes anyway (row-v2 region, decimal or
-       bytes column): the scan path reads less. Remember the verdict. */
+  if (h_rp[0] * 8 > rgn.n_kv) {
+    /* mostly rows that need the row bytes anyway (row-v2 region, wide
+       decimal or bytes column): the scan path reads less. Remember the
+       verdict. Decimal rows are not counted: k_plane_hash reads them from
+       the plane, and the simple consumer declines per request. */
     hipFree(p.val);
     hipFree(p.st);
     slot = DevRegion::ColPlane{};
     slot.col_id = col_id;
     return nullptr;
   }
-  p.n_rowparse = h_rp;
+  p.n_rowparse = h_rp[0];
+  p.n_dec = h_rp[1];
   slot = p;
   rgn.plane_bytes += cost;
   if (built) (*built)++;
@@ -3238,6 +3250,452 @@ int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
     }
   switch (plan.n_aggs) {
     case 1: CASE(1, 4); break;
+    case 2: CASE(2, 2); break;
+    case 3: CASE(3, 2); break;
+    case 4: CASE(4, 2); break;
+    default: CASE(COPR_MAX_AGGS, 1); break;
+  }
+  #undef CASE
+  return (int)hipGetLastError();
+}
+
+/* ---------------- hash aggregation over column planes --------
+ * The group-slot selection, the per-aggregate update and the LDS-table flush
+ * below restate what the hash instantiations of k_scan_agg / k_scan_agg_pipe
+ * do inline, so that a group lands in the same slot with the same
+ * accumulator bits whichever kernel saw the row. */
+
+struct HashSlot { SimpleAggAcc *acc; unsigned long long *ext; };
+
+__device__ static inline uint64_t d_group_hash(int64_t key) {
+  uint64_t h = (uint64_t)key * 0x9E3779B97F4A7C15ull;
+  return h ^ (h >> 29);
+}
+
+/* find-or-claim key's slot in the global open-addressed table; a full table
+   raises ht.error[0] and returns a null acc (the host grows and retries).
+   na = the plan's n_aggs: the accumulator arrays are laid out with that
+   stride, whatever NAGGS the kernel instance unrolls to. */
+__device__ static inline HashSlot d_hash_global_slot(const HashAggTable &ht,
+                                                     uint32_t table_size,
+                                                     uint32_t na,
+                                                     int64_t key) {
+  const unsigned long long EMPTY = 0x8000000000000000ull;
+  HashSlot hs{nullptr, nullptr};
+  uint32_t mask = table_size - 1u;
+  uint32_t slot = (uint32_t)(d_group_hash(key) & mask);
+  for (uint32_t probe = 0; ; probe++) {
+    if (probe > mask) { atomicOr(ht.error, 1u); break; }
+    unsigned long long curk =
+        atomicCAS((unsigned long long *)&ht.keys[slot], EMPTY,
+                  (unsigned long long)key);
+    if (curk == EMPTY) atomicAdd(ht.n_groups, 1ull);
+    if (curk == EMPTY || curk == (unsigned long long)key) {
+      hs.acc = ht.accs + (uint64_t)slot * na;
+      if (ht.ext) hs.ext = ht.ext + (uint64_t)slot * na * 2;
+      break;
+    }
+    slot = (slot + 1) & mask;
+  }
+  return hs;
+}
+
+/* one kept row's accumulator block: NULL/absent keys -> reserved[1],
+   INT64_MIN (the EMPTY sentinel) -> reserved[0], everything else the block's
+   LDS pre-aggregation table first (128-bit accumulators, so never for a row
+   that may need a 256-bit add) and the global table when that is full */
+__device__ static inline HashSlot d_hash_row_slot(
+    const HashAggTable &ht, uint32_t table_size, uint32_t na, bool grp_found,
+    bool grp_null, int64_t grp_v, bool row_wide, long long *lkeys,
+    SimpleAggAcc *laccs, uint32_t lslots) {
+  HashSlot hs{nullptr, nullptr};
+  if (!grp_found || grp_null) {
+    atomicAdd(&ht.rsvd_seen[1], 1ull);
+    hs.acc = ht.reserved + 1 * na;
+    if (ht.rsvd_ext) hs.ext = ht.rsvd_ext + 1 * na * 2;
+    return hs;
+  }
+  if (grp_v == (long long)0x8000000000000000ll) {
+    atomicAdd(&ht.rsvd_seen[0], 1ull);
+    hs.acc = ht.reserved;
+    if (ht.rsvd_ext) hs.ext = ht.rsvd_ext;
+    return hs;
+  }
+  if (lslots && !row_wide) {
+    const unsigned long long EMPTY = 0x8000000000000000ull;
+    uint32_t lmask = lslots - 1u;
+    uint32_t slot = (uint32_t)(d_group_hash(grp_v) & lmask);
+    for (uint32_t probe = 0; probe <= lmask / 2; probe++) {
+      unsigned long long curk =
+          atomicCAS((unsigned long long *)&lkeys[slot], EMPTY,
+                    (unsigned long long)grp_v);
+      if (curk == EMPTY || curk == (unsigned long long)grp_v) {
+        hs.acc = laccs + (uint64_t)slot * na;
+        return hs;
+      }
+      slot = (slot + 1) & lmask;
+    }
+  }
+  return d_hash_global_slot(ht, table_size, na, grp_v);
+}
+
+/* one aggregate's contribution to its accumulator (LDS or global; ext = the
+   two high limbs when the accumulator is 256-bit). A 256-bit accumulator
+   must see every add as i256: a narrow negative i128 add would not borrow
+   from the ext limbs. False = a wide value met a 128-bit accumulator. */
+__device__ static inline bool d_hash_update(const DevAggSpec &sp,
+                                            SimpleAggAcc *acc,
+                                            unsigned long long *ext,
+                                            int64_t v, __int128 vw,
+                                            bool dec_wide) {
+  atomicAdd(&acc->cnt, 1ull);
+  if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_DEC) {
+    if (ext)
+      atomic_add_i256(&acc->sum_lo, &acc->sum_hi, ext,
+                      dec_wide ? vw : (__int128)v);
+    else if (dec_wide)
+      return false;
+    else
+      atomic_add_i128(&acc->sum_lo, &acc->sum_hi, v);
+  } else if (sp.kind == DAGG_MAX_INT || sp.kind == DAGG_MIN_INT) {
+    atomicMax(&acc->sum_lo, d_fold_xform(sp.kind, v, sp.col_unsigned));
+  }
+  return true;
+}
+
+/* epilogue: merge the block's LDS pre-aggregation table into the global one */
+template <int NAGGS>
+__device__ static inline void d_hash_lds_flush(const ScanPlan &plan,
+                                               const HashAggTable &ht,
+                                               const long long *lkeys,
+                                               const SimpleAggAcc *laccs,
+                                               uint32_t lslots) {
+  const uint32_t na = min((uint32_t)plan.n_aggs, (uint32_t)NAGGS);
+  for (uint32_t s = threadIdx.x; s < lslots; s += blockDim.x) {
+    long long key = lkeys[s];
+    if (key == (long long)0x8000000000000000ll) continue;
+    HashSlot gs = d_hash_global_slot(ht, plan.table_size, na, key);
+    if (!gs.acc) continue;
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++) {
+      if ((uint32_t)a >= na) continue;
+      const SimpleAggAcc la = laccs[s * na + a];
+      const int32_t kind = plan.aggs[a].kind;
+      if (la.cnt) atomicAdd(&gs.acc[a].cnt, la.cnt);
+      if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT) {
+        if (la.sum_lo) atomicMax(&gs.acc[a].sum_lo, la.sum_lo);
+        continue;
+      }
+      if (la.sum_lo | la.sum_hi) {
+        if (gs.ext) {
+          atomic_add_i256(&gs.acc[a].sum_lo, &gs.acc[a].sum_hi,
+                          gs.ext + a * 2,
+                          (__int128)(((unsigned __int128)la.sum_hi << 64) |
+                                     la.sum_lo));
+        } else {
+          unsigned long long old = atomicAdd(&gs.acc[a].sum_lo, la.sum_lo);
+          long long carry = (old + la.sum_lo < old) ? 1 : 0;
+          long long hi_add = (long long)la.sum_hi + carry;
+          if (hi_add) atomicAdd(&gs.acc[a].sum_hi, (unsigned long long)hi_add);
+        }
+      }
+    }
+  }
+}
+
+/* sum(decimal) channel: what AggColView carries for the column. CH_DEC = v is
+ * the cell's scaled value (an i128 for a 19..38-digit cell, CH_WIDE) with
+ * frac digits; CH_BADTYPE = a non-NULL cell that holds no decimal, or a wide
+ * payload that does not parse: the scan kernels fail those at the contribute
+ * site, that is only when the row is kept. */
+enum { CH_DEC = 8, CH_WIDE = 16, CH_BADTYPE = 32 };
+struct DecRes { __int128 v; uint32_t fl; int32_t frac; };
+
+/* decimal want of d_plane_resolve: ROWPARSE rows of a sum(decimal) column
+ * (wide decimals, row-v2 rows, cells of another type) from the row bytes.
+ * Kept apart from the int/real resolver so that k_plane_agg's code does not
+ * change. Row-v2 cells parse as in d_v2_collect: a payload that is no
+ * <= 18-digit decimal fails the request. */
+__device__ __noinline__ static DecRes d_plane_resolve_dec(
+    const uint8_t *dirp, uint64_t row, int64_t col_id,
+    const uint8_t *vals, const uint64_t *val_offs) {
+  DecRes dr{0, 0, 0};
+  uint64_t o0 = val_offs[row], o1 = val_offs[row + 1];
+  const uint8_t *vp = vals + o0;
+  uint32_t vlen = (uint32_t)(o1 - o0);
+  uint32_t dir8 = dirp ? (uint32_t)dirp[row] : 0xFEu;
+  CellView cell;
+  int loc = d_col_locate(vp, vlen, dir8, col_id, &cell);
+  if (loc == LOC_ERR) {
+    dr.fl = CH_ERR;
+  } else if (loc == LOC_V2) {
+    V2Row r;
+    uint32_t s, e;
+    if (!d_v2_parse(vp, vlen, &r)) { dr.fl = CH_ERR; return dr; }
+    int fs = d_v2_find(r, col_id, &s, &e);
+    if (fs < 0) return dr;
+    dr.fl = CH_FOUND;
+    if (fs == 0) { dr.fl |= CH_NULL; return dr; }
+    int64_t sc;
+    if (!d_decimal_scaled(r.vals + s, e - s, &sc, &dr.frac)) {
+      dr.fl |= CH_ERR;
+      return dr;
+    }
+    dr.v = sc;
+    dr.fl |= CH_DEC;
+  } else if (loc == LOC_CELL) {
+    dr.fl = CH_FOUND;
+    if (cell.is_null) {
+      dr.fl |= CH_NULL;
+    } else if (cell.has_dec) {
+      dr.v = cell.dscaled; dr.frac = cell.dfrac; dr.fl |= CH_DEC;
+    } else if (cell.dwide) {
+      dr.fl |= CH_WIDE;
+      if (d_decimal_scaled128(cell.dwide, cell.dwide_rem, &dr.v, &dr.frac))
+        dr.fl |= CH_DEC;
+      else
+        dr.fl |= CH_BADTYPE;
+    } else if (cell.has_int || cell.has_real) {
+      dr.fl |= CH_BADTYPE;
+    } else {
+      dr.fl |= CH_ERR;
+    }
+  }
+  return dr;
+}
+
+__device__ static inline DecRes d_plane_dec_chan(
+    const PlaneRef &pr, uint32_t st, int64_t pv, uint64_t row, int64_t col_id,
+    const uint8_t *vals, const uint64_t *val_offs) {
+  if (st >= PST_DEC0)
+    return DecRes{(__int128)pv, CH_FOUND | CH_DEC, (int32_t)(st - PST_DEC0)};
+  switch (st) {
+    case PST_INT:
+    case PST_REAL:   return DecRes{0, CH_FOUND | CH_BADTYPE, 0};
+    case PST_NULL:   return DecRes{0, CH_FOUND | CH_NULL, 0};
+    case PST_ABSENT: return DecRes{0, 0, 0};
+    case PST_ERR:    return DecRes{0, CH_ERR, 0};
+    default:
+      return d_plane_resolve_dec(pr.dir, row, col_id, vals, val_offs);
+  }
+}
+
+/* FastHashAgg (int group key) over column planes. Loads as in k_plane_agg:
+ * per lane 16 B (two rows) of every distinct referenced value plane plus the
+ * two state bytes, UNR pairs issued before any row work, tail pairs clamped
+ * into the planes' slack. The keep decision is d_filter_keep /
+ * d_filter2_keep; slot selection, accumulation and the flush are the helpers
+ * above. Parse errors: a PST_ERR row or a failed ROWPARSE resolve raises
+ * ht.error[1] whether or not the row is kept; sum(decimal) scaling errors and
+ * type mismatches only for a kept row. The grid is capped by the host so the
+ * number of LDS-table flushes stays bounded. Dynamic LDS: lslots keys, then
+ * lslots * n_aggs accumulators. NAGGS >= n_aggs is the unroll bound only:
+ * every accumulator array keeps the plan's n_aggs stride. */
+template <int NAGGS, int UNR>
+__global__ void __launch_bounds__(256)
+k_plane_hash(ScanPlan plan, PlaneSet ps, HashAggTable ht,
+             const uint8_t *__restrict__ vals,
+             const uint64_t *__restrict__ val_offs, uint64_t n_rows) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  const uint32_t LSLOTS = plan.lds_agg_slots;
+  long long *lkeys = (long long *)lds;
+  SimpleAggAcc *laccs = (SimpleAggAcc *)(lkeys + LSLOTS);
+  const uint32_t na = min((uint32_t)plan.n_aggs, (uint32_t)NAGGS);
+  for (uint32_t s = threadIdx.x; s < LSLOTS; s += 256u) {
+    lkeys[s] = (long long)0x8000000000000000ll;
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++)
+      if ((uint32_t)a < na) laccs[s * na + a] = SimpleAggAcc{0, 0, 0};
+  }
+  __syncthreads();
+  bool any_parse_err = false;
+
+  const uint64_t n_pairs = (n_rows + 1) >> 1;
+  const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * 256u * UNR + threadIdx.x;
+       p0 < n_pairs; p0 += step) {
+    /* all loads first (clamped, unconditional per distinct plane) */
+    longlong2 gv[UNR], fv[UNR], f2v[UNR], av[NAGGS][UNR];
+    uint16_t gs[UNR], fs[UNR], f2s[UNR], ast[NAGGS][UNR];
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = min(p0 + (uint64_t)u * 256u, n_pairs - 1);
+      gv[u] = ((const longlong2 *)ps.g.val)[p];
+      gs[u] = ((const uint16_t *)ps.g.st)[p];
+      fv[u] = make_longlong2(0, 0); fs[u] = 0;
+      f2v[u] = make_longlong2(0, 0); f2s[u] = 0;
+      if (ps.f.val) {
+        fv[u] = ((const longlong2 *)ps.f.val)[p];
+        fs[u] = ((const uint16_t *)ps.f.st)[p];
+      }
+      if (ps.f2.val) {
+        f2v[u] = ((const longlong2 *)ps.f2.val)[p];
+        f2s[u] = ((const uint16_t *)ps.f2.st)[p];
+      }
+      #pragma unroll
+      for (int a = 0; a < NAGGS; a++) {
+        av[a][u] = make_longlong2(0, 0); ast[a][u] = 0;
+        if (ps.a[a].val && ps.a_src[a] == 0) {
+          av[a][u] = ((const longlong2 *)ps.a[a].val)[p];
+          ast[a][u] = ((const uint16_t *)ps.a[a].st)[p];
+        }
+      }
+    }
+    /* a column referenced twice was loaded once: copy the registers */
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      #pragma unroll
+      for (int a = 0; a < NAGGS; a++) {
+        const int32_t src = ps.a_src[a];
+        if (src == 1) { av[a][u] = gv[u]; ast[a][u] = gs[u]; }
+        else if (src == 2) { av[a][u] = fv[u]; ast[a][u] = fs[u]; }
+        else if (src == 3) { av[a][u] = f2v[u]; ast[a][u] = f2s[u]; }
+        #pragma unroll
+        for (int b = 0; b < a; b++)
+          if (src == 4 + b) { av[a][u] = av[b][u]; ast[a][u] = ast[b][u]; }
+      }
+    }
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = p0 + (uint64_t)u * 256u;
+      #pragma unroll
+      for (int h = 0; h < 2; h++) {
+        uint64_t row = p * 2 + h;
+        if (p >= n_pairs || row >= n_rows) continue;
+        ChanRes f{0, 0}, f2{0, 0}, ag[NAGGS];
+        DecRes dg[NAGGS];
+        ChanRes g = d_plane_chan(ps.g, (gs[u] >> (8 * h)) & 0xFFu,
+                                 h ? gv[u].y : gv[u].x, row, plan.group_col_id,
+                                 plan.group_col_unsigned != 0, 0, vals,
+                                 val_offs);
+        if (ps.f.val)
+          f = d_plane_chan(ps.f, (fs[u] >> (8 * h)) & 0xFFu,
+                           h ? fv[u].y : fv[u].x, row, plan.filter_col_id,
+                           plan.filter_col_unsigned != 0,
+                           plan.filter_is_real ? 1 : 0, vals, val_offs);
+        if (ps.f2.val)
+          f2 = d_plane_chan(ps.f2, (f2s[u] >> (8 * h)) & 0xFFu,
+                            h ? f2v[u].y : f2v[u].x, row, plan.filter2_col_id,
+                            plan.filter2_col_unsigned != 0,
+                            plan.filter2_is_real ? 1 : 0, vals, val_offs);
+        uint32_t fl_or = g.fl | f.fl | f2.fl;
+        #pragma unroll
+        for (int a = 0; a < NAGGS; a++) {
+          ag[a] = ChanRes{0, 0};
+          dg[a] = DecRes{0, 0, 0};
+          if (ps.a[a].val) {
+            const uint32_t st = (ast[a][u] >> (8 * h)) & 0xFFu;
+            const int64_t pv = h ? av[a][u].y : av[a][u].x;
+            if (plan.aggs[a].kind == DAGG_SUM_DEC) {
+              dg[a] = d_plane_dec_chan(ps.a[a], st, pv, row,
+                                       plan.aggs[a].col_id, vals, val_offs);
+              ag[a].fl = dg[a].fl;
+            } else {
+              ag[a] = d_plane_chan(ps.a[a], st, pv, row, plan.aggs[a].col_id,
+                                   plan.aggs[a].col_unsigned != 0,
+                                   plan.aggs[a].kind == DAGG_COUNT_COL ? 3 : 2,
+                                   vals, val_offs);
+            }
+          }
+          fl_or |= ag[a].fl;
+        }
+        if (fl_or & CH_ERR) { any_parse_err = true; continue; }
+        if (!(d_filter_keep(plan, (f.fl & CH_FOUND) != 0,
+                            (f.fl & CH_NULL) != 0, f.v) &&
+              d_filter2_keep(plan, (f2.fl & CH_FOUND) != 0,
+                             (f2.fl & CH_NULL) != 0, f2.v)))
+          continue;
+        /* conservative wide-decimal pre-pass: a row that may need a 256-bit
+           add must take a global slot (the LDS table is 128-bit) */
+        bool row_wide = false;
+        #pragma unroll
+        for (int a = 0; a < NAGGS; a++) {
+          if (plan.aggs[a].kind != DAGG_SUM_DEC ||
+              (ag[a].fl & (CH_FOUND | CH_NULL)) != CH_FOUND)
+            continue;
+          if (ag[a].fl & CH_WIDE) { row_wide = true; continue; }
+          if (!(ag[a].fl & CH_DEC)) continue;
+          int d = plan.aggs[a].target_frac - dg[a].frac;
+          if (d > 18) { row_wide = true; continue; }
+          if (d > 0) {
+            int64_t lim = (int64_t)(0x7FFFFFFFFFFFFFFFll);
+            for (int t = 0; t < d; t++) lim /= 10;
+            const int64_t sc = (int64_t)dg[a].v;
+            if (sc > lim || sc < -lim) row_wide = true;
+          }
+        }
+        HashSlot hs = d_hash_row_slot(
+            ht, plan.table_size, na, (g.fl & CH_FOUND) != 0,
+            (g.fl & CH_NULL) != 0, g.v, row_wide, lkeys, laccs, LSLOTS);
+        #pragma unroll
+        for (int a = 0; a < NAGGS; a++) {
+          const DevAggSpec &sp = plan.aggs[a];
+          bool dec_wide = false;       /* value does not fit a scaled i64 */
+          __int128 vw = 0;
+          int64_t v = 0;
+          if ((uint32_t)a >= na) continue;
+          if (sp.kind != DAGG_COUNT_ROWS) {
+            if ((ag[a].fl & (CH_FOUND | CH_NULL)) != CH_FOUND) continue;
+            if (sp.kind == DAGG_SUM_DEC) {
+              const bool okd = (ag[a].fl & CH_DEC) != 0;
+              int d = okd ? sp.target_frac - dg[a].frac : -1;
+              if (d < 0 || d > 38) { any_parse_err = true; continue; }
+              __int128 sv = dg[a].v;
+              const __int128 LIM =
+                  (__int128)(((unsigned __int128)~(unsigned __int128)0) >> 1) / 10;
+              bool ovf = false;
+              for (int t = 0; t < d; t++) {
+                if (sv > LIM || sv < -LIM) { ovf = true; break; }
+                sv *= 10;
+              }
+              if (ovf) { any_parse_err = true; continue; }  /* > 38 digits */
+              if (sv >= (__int128)INT64_MIN && sv <= (__int128)INT64_MAX) {
+                v = (int64_t)sv;
+              } else {
+                vw = sv;
+                dec_wide = true;
+              }
+            } else {
+              v = ag[a].v;
+            }
+          }
+          if (hs.acc &&
+              !d_hash_update(sp, hs.acc + a, hs.ext ? hs.ext + a * 2 : nullptr,
+                             v, vw, dec_wide))
+            any_parse_err = true;     /* no ext buffers: loud */
+        }
+      }
+    }
+  }
+
+  if (LSLOTS) {
+    __syncthreads();
+    d_hash_lds_flush<NAGGS>(plan, ht, lkeys, laccs, LSLOTS);
+  }
+  if (any_parse_err) atomicOr(ht.error + 1, 1u);
+}
+
+int dev_plane_hash_launch(const ScanPlan &plan, const PlaneSet &ps,
+                          const DevRegion &rgn, const HashAggTable &ht,
+                          void *stream) {
+  if (!rgn.n_kv) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t n_pairs = (rgn.n_kv + 1) >> 1;
+  const uint32_t lds_b =
+      plan.lds_agg_slots *
+      (8u + (uint32_t)plan.n_aggs * (uint32_t)sizeof(SimpleAggAcc));
+  /* every block flushes its LDS table once: cap the grid at what the device
+     keeps resident at 256 CUs x 8 blocks, and let the blocks stride */
+  #define CASE(N, U)                                                         \
+    {                                                                        \
+      uint64_t nb = (n_pairs + 256u * U - 1) / (256u * U);                   \
+      uint32_t grid = (uint32_t)(nb < 2048 ? nb : 2048);                     \
+      hipLaunchKernelGGL((k_plane_hash<N, U>), dim3(grid), dim3(256), lds_b, \
+                         s, plan, ps, ht, rgn.d_vals, rgn.d_val_offs,        \
+                         rgn.n_kv);                                          \
+    }
+  switch (plan.n_aggs) {
+    case 1: CASE(1, 2); break;
     case 2: CASE(2, 2); break;
     case 3: CASE(3, 2); break;
     case 4: CASE(4, 2); break;

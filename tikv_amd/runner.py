@@ -546,6 +546,12 @@ class Engine:
         return (self._lib.copr_engine_plane_launches(self._h),
                 self._lib.copr_engine_plane_builds(self._h))
 
+    def hash_plane_launches(self):
+        """Launches of the plane hash-aggregation kernel (one per region per
+        attempt) since the engine was created. plane_stats()[0] does not
+        count them; plane_stats()[1] counts the planes they built."""
+        return self._lib.copr_engine_hash_plane_launches(self._h)
+
     def close(self):
         if self._h:
             self._lib.copr_engine_destroy(self._h)
