@@ -104,6 +104,11 @@ uint64_t    copr_engine_plane_builds(const copr_engine *);
  * apart: copr_engine_plane_launches stays the simple-aggregate count, while
  * copr_engine_plane_builds counts every build whichever consumer asked. */
 uint64_t    copr_engine_hash_plane_launches(const copr_engine *);
+/* Narrow filter planes: per-region launches of the narrow
+ * filter+count kernel (copr_engine_plane_launches counts them too), and
+ * narrow planes built (copr_engine_plane_builds does not count them). */
+uint64_t    copr_engine_narrow_launches(const copr_engine *);
+uint64_t    copr_engine_narrow_builds(const copr_engine *);
 
 /* ---- checksum (REQ_TYPE_CHECKSUM = 105; src/coprocessor/checksum.rs:59-114) ----
  * CRC-64/XZ per KV over key||value, XOR-folded (order-independent). */

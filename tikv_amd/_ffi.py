@@ -164,6 +164,10 @@ def load_lib():
     lib.copr_engine_plane_builds.argtypes = [C.c_void_p]
     lib.copr_engine_hash_plane_launches.restype = C.c_uint64
     lib.copr_engine_hash_plane_launches.argtypes = [C.c_void_p]
+    lib.copr_engine_narrow_launches.restype = C.c_uint64
+    lib.copr_engine_narrow_launches.argtypes = [C.c_void_p]
+    lib.copr_engine_narrow_builds.restype = C.c_uint64
+    lib.copr_engine_narrow_builds.argtypes = [C.c_void_p]
     lib.copr_checksum.restype = C.c_int
     lib.copr_checksum.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32,
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),

@@ -75,6 +75,8 @@ extern "C" void copr_engine_destroy(copr_engine *eng) {
   }
   hipFree(eng->d_simple_acc);
   hipFree(eng->d_simple_ext);
+  hipFree(eng->d_fcn_state);
+  if (eng->h_fcn_out) hipHostFree(eng->h_fcn_out);
   if (eng->stream) hipStreamDestroy(eng->stream);
   delete eng;
 }
@@ -89,6 +91,14 @@ extern "C" uint64_t copr_engine_plane_builds(const copr_engine *eng) {
 
 extern "C" uint64_t copr_engine_hash_plane_launches(const copr_engine *eng) {
   return eng ? eng->hash_plane_launches : 0;
+}
+
+extern "C" uint64_t copr_engine_narrow_launches(const copr_engine *eng) {
+  return eng ? eng->narrow_launches : 0;
+}
+
+extern "C" uint64_t copr_engine_narrow_builds(const copr_engine *eng) {
+  return eng ? eng->narrow_builds : 0;
 }
 
 /* ---------------- region ---------------- */
@@ -1039,10 +1049,21 @@ static bool plane_set_used(const PlaneSet &ps) {
    wire_celldir applies.
    hash = the k_plane_hash consumer: it also wires the group column, reads
    decimal rows from the plane, and may spend the region's full value bytes
-   on planes where the simple consumer stops at half. */
+   on planes where the simple consumer stops at half.
+   nu (simple consumer only): when the wiring has the k_plane_fc shape, the
+   filter plane's narrow companion is built here on first use and the filter
+   folded into its domain; nu->p stays null when the region
+   keeps k_plane_fc. */
+struct NarrowUse {
+  const DevRegion::ColPlane *p = nullptr;
+  NarrowFcArgs nf{};
+};
+
 static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
-                       PlaneSet *ps, bool hash = false) {
+                       PlaneSet *ps, bool hash = false,
+                       NarrowUse *nu = nullptr) {
   *ps = PlaneSet{};
+  if (nu) *nu = NarrowUse{};
   if (!dev.n_kv) return false;
   uint64_t budget = hash ? dev.val_bytes : dev.val_bytes / 2;
   if (const char *e = getenv("COPR_PLANE_BUDGET_MB"))
@@ -1086,6 +1107,18 @@ static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
       else
         for (int b = 0; b < a; b++)
           if (ps->a[b].val == r.val) { ps->a_src[a] = 4 + b; break; }
+    }
+  }
+  PlaneFcArgs fa;
+  if (nu && !hash && !getenv("COPR_NO_NARROW") &&
+      dev_plane_fc_shape(sp, *ps, &fa)) {
+    const DevRegion::ColPlane *np = dev_colplane_narrow(
+        dev, sp.filter_col_id, budget, eng->stream, &eng->narrow_builds);
+    NarrowFcArgs nf;
+    if (np && narrow_fc_fold(fa, np->nar_base, np->nar_nmax,
+                             sp.filter_col_unsigned != 0, &nf)) {
+      nu->p = np;
+      nu->nf = nf;
     }
   }
   return true;
@@ -2332,53 +2365,134 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
       }
       SimpleAggAcc *d_acc = eng->d_simple_acc;
       unsigned long long *d_ext = nullptr;
-      HIP_TRY(hipMemsetAsync(d_acc, 0, sizeof(SimpleAggAcc) * (COPR_MAX_AGGS + 1),
-                             eng->stream), "acc memset");
       bool any_dec = false;
       for (int a = 0; a < pl.sp.n_aggs; a++)
         if (pl.sp.aggs[a].kind == DAGG_SUM_DEC || pl.sp.aggs[a].kind == DAGG_SUM_INT)
           any_dec = true;
-      if (any_dec) {
-        d_ext = eng->d_simple_ext;
-        HIP_TRY(hipMemsetAsync(d_ext, 0, COPR_MAX_AGGS * 16, eng->stream),
-                "acc ext memset");
-      }
-      /* column planes: decided per region; a missing plane is built here,
-         before the timed events, so time_processed_ns stays the query */
+      /* column planes: decided per region; a missing plane, and the filter
+         plane's narrow companion, is built here, before the timed events, so
+         time_processed_ns stays the query */
       std::vector<PlaneSet> psets;
+      std::vector<NarrowUse> nuse;
       if (!getenv("COPR_NO_PLANES") && plane_plan_ok(pl.sp)) {
         psets.resize(n_regions);
+        nuse.resize(n_regions);
         for (uint32_t rg = 0; rg < n_regions; rg++)
-          if (!plane_wire(eng, regions[rg]->dev, pl.sp, &psets[rg]))
+          if (!plane_wire(eng, regions[rg]->dev, pl.sp, &psets[rg], false,
+                          &nuse[rg])) {
             psets[rg] = PlaneSet{};
+            nuse[rg] = NarrowUse{};
+          }
       }
-      hipEventRecord(ev_a, eng->stream);
-      for (uint32_t rg = 0; rg < n_regions; rg++) {
-        ScanPlan sp = pl.sp;
-        sp.simple_ext = d_ext;
-        wire_celldir(&sp, regions[rg]->dev);
-        int e;
-        if (!psets.empty() && plane_set_used(psets[rg])) {
-          e = dev_plane_agg_launch(sp, psets[rg], regions[rg]->dev, d_acc,
-                                   eng->stream);
-          eng->plane_launches++;
+      uint32_t fcn_grid = 0;              /* diagnostic: cap k_plane_fcn's grid */
+      if (const char *g = getenv("COPR_NARROW_GRID"))
+        fcn_grid = (uint32_t)strtoul(g, nullptr, 10);
+      /* one-dispatch step: every region takes k_plane_fcn, so
+         the whole result is one count, which the last launch's last block
+         hands to the pinned host word while it re-zeroes the device words.
+         No memset and no copy in the steady state. */
+      bool one_dispatch = n_regions > 0 && !nuse.empty() &&
+                          !getenv("COPR_NARROW_NO_FINALIZE");
+      for (uint32_t rg = 0; one_dispatch && rg < n_regions; rg++)
+        if (!nuse[rg].p) one_dispatch = false;
+      if (one_dispatch && !eng->d_fcn_state) {
+        /* first use; on failure the request takes the usual sequence */
+        void *d = nullptr, *h = nullptr;
+        if (hipMalloc(&d, COPR_FCN_STATE_WORDS * 8) == hipSuccess &&
+            hipHostMalloc(&h, sizeof(unsigned long long),
+                          hipHostMallocDefault) == hipSuccess) {
+          eng->d_fcn_state = (unsigned long long *)d;
+          eng->h_fcn_out = (unsigned long long *)h;
+          eng->fcn_dirty = true;          /* zeroed below */
         } else {
-          pick_tiling(regions[rg]->dev, &sp);
-          e = dev_scan_launch(sp, regions[rg]->dev, d_acc, nullptr, nullptr, eng->stream);
+          (void)hipGetLastError();
+          hipFree(d);
+          one_dispatch = false;
         }
-        if (e) return SET_ERR(COPR_ERR_INTERNAL, "scan launch failed");
       }
-      hipEventRecord(ev_b, eng->stream);
-      timed = true;
+      if (one_dispatch && eng->fcn_dirty) {
+        if (hipMemsetAsync(eng->d_fcn_state, 0, COPR_FCN_STATE_WORDS * 8,
+                           eng->stream) == hipSuccess) {
+          eng->fcn_dirty = false;
+        } else {
+          (void)hipGetLastError();
+          one_dispatch = false;
+        }
+      }
       SimpleAggAcc h_acc[COPR_MAX_AGGS + 1];
       unsigned long long h_ext[COPR_MAX_AGGS * 2] = {0};
-      hipError_t ce = hipMemcpyAsync(h_acc, d_acc, sizeof(h_acc), hipMemcpyDeviceToHost,
+      if (one_dispatch) {
+        unsigned long long *d_cnt = eng->d_fcn_state;
+        unsigned int *d_ticket = (unsigned int *)(
+            eng->d_fcn_state + COPR_FCN_SLOTS * COPR_FCN_SLOT_STRIDE);
+        hipEventRecord(ev_a, eng->stream);
+        for (uint32_t rg = 0; rg < n_regions; rg++) {
+          const bool last = rg + 1 == n_regions;
+          int e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf,
+                                       regions[rg]->dev.n_kv, d_cnt,
+                                       COPR_FCN_SLOTS,
+                                       last ? d_ticket : nullptr,
+                                       last ? eng->h_fcn_out : nullptr,
+                                       fcn_grid, eng->stream);
+          eng->plane_launches++;
+          eng->narrow_launches++;
+          if (e) {
+            eng->fcn_dirty = true;
+            return SET_ERR(COPR_ERR_INTERNAL, "narrow plane launch failed");
+          }
+        }
+        hipEventRecord(ev_b, eng->stream);
+        timed = true;
+        hipError_t ce = hipStreamSynchronize(eng->stream);
+        if (ce != hipSuccess) {
+          eng->fcn_dirty = true;
+          return SET_ERR(COPR_ERR_INTERNAL, hipGetErrorString(ce));
+        }
+        memset(h_acc, 0, sizeof(h_acc));
+        h_acc[0].cnt = *(volatile unsigned long long *)eng->h_fcn_out;
+      } else {
+        HIP_TRY(hipMemsetAsync(d_acc, 0,
+                               sizeof(SimpleAggAcc) * (COPR_MAX_AGGS + 1),
+                               eng->stream), "acc memset");
+        if (any_dec) {
+          d_ext = eng->d_simple_ext;
+          HIP_TRY(hipMemsetAsync(d_ext, 0, COPR_MAX_AGGS * 16, eng->stream),
+                  "acc ext memset");
+        }
+        hipEventRecord(ev_a, eng->stream);
+        for (uint32_t rg = 0; rg < n_regions; rg++) {
+          ScanPlan sp = pl.sp;
+          sp.simple_ext = d_ext;
+          wire_celldir(&sp, regions[rg]->dev);
+          int e;
+          if (!nuse.empty() && nuse[rg].p) {
+            /* a narrow region beside regions that are not: same kernel, the
+               count joins the other regions' in the usual accumulator */
+            e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf,
+                                     regions[rg]->dev.n_kv, &d_acc[0].cnt, 1,
+                                     nullptr, nullptr, fcn_grid, eng->stream);
+            eng->plane_launches++;
+            eng->narrow_launches++;
+          } else if (!psets.empty() && plane_set_used(psets[rg])) {
+            e = dev_plane_agg_launch(sp, psets[rg], regions[rg]->dev, d_acc,
                                      eng->stream);
-      if (ce == hipSuccess && d_ext)
-        ce = hipMemcpyAsync(h_ext, d_ext, COPR_MAX_AGGS * 16,
-                            hipMemcpyDeviceToHost, eng->stream);
-      if (ce == hipSuccess) ce = hipStreamSynchronize(eng->stream);
-      if (ce != hipSuccess) return SET_ERR(COPR_ERR_INTERNAL, hipGetErrorString(ce));
+            eng->plane_launches++;
+          } else {
+            pick_tiling(regions[rg]->dev, &sp);
+            e = dev_scan_launch(sp, regions[rg]->dev, d_acc, nullptr, nullptr, eng->stream);
+          }
+          if (e) return SET_ERR(COPR_ERR_INTERNAL, "scan launch failed");
+        }
+        hipEventRecord(ev_b, eng->stream);
+        timed = true;
+        hipError_t ce = hipMemcpyAsync(h_acc, d_acc, sizeof(h_acc), hipMemcpyDeviceToHost,
+                                       eng->stream);
+        if (ce == hipSuccess && d_ext)
+          ce = hipMemcpyAsync(h_ext, d_ext, COPR_MAX_AGGS * 16,
+                              hipMemcpyDeviceToHost, eng->stream);
+        if (ce == hipSuccess) ce = hipStreamSynchronize(eng->stream);
+        if (ce != hipSuccess) return SET_ERR(COPR_ERR_INTERNAL, hipGetErrorString(ce));
+      }
       if (h_acc[COPR_MAX_AGGS].cnt & 1)
         return SET_ERR(COPR_ERR_STORAGE, "row parse error on device");
       /* encode the single result row */

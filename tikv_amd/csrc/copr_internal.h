@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/copr_types.h"   /* scalar sig / tp enums */
+#include "plane_fold.h"                  /* CMP_*, PlaneFcArgs, NarrowFcArgs */
 
 namespace copr {
 
@@ -48,6 +49,16 @@ struct DevRegion {
     uint8_t *st = nullptr;         /* [n_kv] (+ tail slack), PST_* */
     uint64_t n_rowparse = 0;       /* rows left to query time (PST_ROWPARSE) */
     uint64_t n_dec = 0;            /* rows holding a decimal (PST_DEC0 + frac) */
+    /* narrow companion: (uint)(val - nar_base) in nar_w bytes
+       per row, for a plane whose every row is PST_INT and whose value range
+       fits 32 bits. Tried once, by the first filter+count request wired to
+       this plane; a declined verdict (other states present, range too wide,
+       over budget, allocation failed) is remembered. */
+    void *nar = nullptr;           /* [n_kv] x nar_w (+ tail slack) */
+    uint32_t nar_w = 0;            /* 1, 2 or 4 */
+    int32_t nar_verdict = 0;       /* NAR_UNTRIED / NAR_DECLINED / NAR_BUILT */
+    int64_t nar_base = 0;          /* signed minimum of the plane's values */
+    uint64_t nar_nmax = 0;         /* max - min */
   };
   ColPlane planes[COPR_MAX_PLANES];
   int32_t n_planes = 0;
@@ -65,9 +76,9 @@ enum { PST_INT = 0, PST_REAL, PST_NULL, PST_ABSENT, PST_ROWPARSE, PST_ERR };
    other consumer treats the state as ROWPARSE. Wide decimals (19..38 digits)
    stay PST_ROWPARSE. */
 enum { PST_DEC0 = 16 };
+enum { NAR_UNTRIED = 0, NAR_DECLINED, NAR_BUILT };
 
-/* compare kinds (order matches oracle CmpKind) */
-enum { CMP_LT = 0, CMP_LE, CMP_GT, CMP_GE, CMP_EQ, CMP_NE };
+/* compare kinds CMP_*: plane_fold.h */
 
 /* device agg kinds */
 enum {
@@ -338,6 +349,30 @@ const DevRegion::ColPlane *dev_colplane_get(DevRegion &rgn, int64_t col_id,
                                             uint64_t budget_bytes,
                                             hipStream_t s, uint64_t *built);
 void dev_colplane_free(DevRegion &rgn);
+/* narrow companion of col_id's plane (which must exist): built on first use
+ * within budget_bytes (synchronous, like dev_colplane_get), null when the
+ * plane was declined. *built is incremented when this call stored one. */
+const DevRegion::ColPlane *dev_colplane_narrow(DevRegion &rgn, int64_t col_id,
+                                               uint64_t budget_bytes,
+                                               hipStream_t s, uint64_t *built);
+/* does the request take k_plane_fc on this wiring? On true *fa is its range
+ * test. */
+bool dev_plane_fc_shape(const ScanPlan &plan, const PlaneSet &ps,
+                        PlaneFcArgs *fa);
+/* filter+count over a narrow plane (narrow_planes.hip): adds the kept rows
+ * to n_slots count words (a power of two <= COPR_FCN_SLOTS), the first at
+ * d_cnt and COPR_FCN_SLOT_STRIDE words apart; their sum is the count. With a
+ * non-null d_ticket the launch finalizes: its last block stores that sum to
+ * *h_out (device-visible pinned host memory) and zeroes the count words and
+ * *d_ticket. grid_cap 0 = the default grid. */
+#define COPR_FCN_SLOTS 64
+#define COPR_FCN_SLOT_STRIDE 16          /* u64 words: one 128 B line each */
+#define COPR_FCN_STATE_WORDS (COPR_FCN_SLOTS * COPR_FCN_SLOT_STRIDE + 16)
+int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
+                         uint64_t n_rows, unsigned long long *d_cnt,
+                         uint32_t n_slots, unsigned int *d_ticket,
+                         unsigned long long *h_out, uint32_t grid_cap,
+                         void *stream);
 /* simple aggregates (mode 1) over column planes instead of the row bytes */
 int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
                          const DevRegion &rgn, SimpleAggAcc *d_simple,
@@ -426,11 +461,22 @@ struct copr_engine {
      memsets, freed in engine destroy */
   copr::SimpleAggAcc *d_simple_acc = nullptr;
   unsigned long long *d_simple_ext = nullptr;
+  /* one-dispatch filter+count over narrow planes: the device
+     count words and, behind them, the ticket word (COPR_FCN_STATE_WORDS u64
+     in all), zero between requests because the finalizing block resets
+     them, and the pinned host
+     word that block delivers the total to. fcn_dirty = a HIP call on that
+     path failed, so the words are memset before their next use. */
+  unsigned long long *d_fcn_state = nullptr;
+  unsigned long long *h_fcn_out = nullptr;
+  bool fcn_dirty = false;
   /* diagnostics (copr_engine_plane_launches / _builds /
-     copr_engine_hash_plane_launches) */
+     copr_engine_hash_plane_launches / _narrow_launches / _narrow_builds) */
   uint64_t plane_launches = 0;
   uint64_t plane_builds = 0;
   uint64_t hash_plane_launches = 0;
+  uint64_t narrow_launches = 0;
+  uint64_t narrow_builds = 0;
 };
 
 struct copr_region {

@@ -2884,6 +2884,7 @@ void dev_colplane_free(DevRegion &rgn) {
   for (int32_t i = 0; i < rgn.n_planes; i++) {
     hipFree(rgn.planes[i].val);
     hipFree(rgn.planes[i].st);
+    hipFree(rgn.planes[i].nar);
     rgn.planes[i] = DevRegion::ColPlane{};
   }
   rgn.n_planes = 0;
@@ -3142,11 +3143,8 @@ k_plane_agg(ScanPlan plan, PlaneSet ps,
  * so the row loop is a handful of VALU ops and the kernel follows the
  * loads. Same results: NULL never keeps, ABSENT takes the request's default
  * fill (keep_absent, decided on the host with the same test), REAL and ERR
- * cells raise the parse-error flag. */
-struct PlaneFcArgs {
-  unsigned long long bias, lo, span;
-  uint32_t invert, keep_absent;
-};
+ * cells raise the parse-error flag. PlaneFcArgs and the fold itself live in
+ * plane_fold.h. */
 
 __global__ void __launch_bounds__(256)
 k_plane_fc(PlaneFcArgs fa, const longlong2 *__restrict__ val,
@@ -3200,29 +3198,15 @@ static bool plane_fc_args(const ScanPlan &plan, const PlaneSet &ps,
       (plan.filter_col_unsigned != 0) != (plan.filter_const_unsigned != 0) ||
       ps.f.n_rowparse)
     return false;
-  const unsigned long long MAXU = ~0ull;
-  fa->bias = plan.filter_col_unsigned ? 0ull : 0x8000000000000000ull;
-  const unsigned long long c =
-      (unsigned long long)plan.filter_const ^ fa->bias;
-  bool empty = false;
-  fa->invert = 0;
-  switch (plan.filter_cmp) {
-    case CMP_LT: empty = c == 0; fa->lo = 0; fa->span = c - 1; break;
-    case CMP_LE: fa->lo = 0; fa->span = c; break;
-    case CMP_GT: empty = c == MAXU; fa->lo = c + 1; fa->span = MAXU - (c + 1); break;
-    case CMP_GE: fa->lo = c; fa->span = MAXU - c; break;
-    case CMP_EQ: fa->lo = c; fa->span = 0; break;
-    default:     fa->lo = c; fa->span = 0; fa->invert = 1; break;   /* NE */
-  }
-  if (empty || plan.filter_const_null) {   /* never true: all-range, inverted */
-    fa->lo = 0; fa->span = MAXU; fa->invert = 1;
-  }
-  unsigned long long mk =
-      (unsigned long long)plan.filter_missing_val ^ fa->bias;
-  fa->keep_absent = (!plan.filter_missing_null &&
-                     (((mk - fa->lo) <= fa->span) != (fa->invert != 0)))
-                        ? 1u : 0u;
+  plane_fc_fold(plan.filter_cmp, plan.filter_const,
+                plan.filter_col_unsigned != 0, plan.filter_const_null != 0,
+                plan.filter_missing_null != 0, plan.filter_missing_val, fa);
   return true;
+}
+
+bool dev_plane_fc_shape(const ScanPlan &plan, const PlaneSet &ps,
+                        PlaneFcArgs *fa) {
+  return plane_fc_args(plan, ps, fa);
 }
 
 int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,

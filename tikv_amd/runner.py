@@ -552,6 +552,13 @@ class Engine:
         count them; plane_stats()[1] counts the planes they built."""
         return self._lib.copr_engine_hash_plane_launches(self._h)
 
+    def narrow_stats(self):
+        """(launches, builds): per-region launches of the narrow filter+count
+        kernel (plane_stats()[0] counts them too) and narrow planes built
+        (plane_stats()[1] does not), since the engine was created."""
+        return (self._lib.copr_engine_narrow_launches(self._h),
+                self._lib.copr_engine_narrow_builds(self._h))
+
     def close(self):
         if self._h:
             self._lib.copr_engine_destroy(self._h)
