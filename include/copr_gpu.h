@@ -109,6 +109,13 @@ uint64_t    copr_engine_hash_plane_launches(const copr_engine *);
  * narrow planes built (copr_engine_plane_builds does not count them). */
 uint64_t    copr_engine_narrow_launches(const copr_engine *);
 uint64_t    copr_engine_narrow_builds(const copr_engine *);
+/* TopN over several order-by columns: requests served by the
+ * multi-key pipeline (monotonic), and for the last of them the rows its
+ * filters kept (m) and the rows that passed the primary-key candidate cut
+ * and had their other keys read (c). Single-key TopN moves none of them. */
+uint64_t    copr_engine_topn_multi_runs(const copr_engine *);
+uint64_t    copr_engine_topn_last_kept(const copr_engine *);
+uint64_t    copr_engine_topn_last_candidates(const copr_engine *);
 
 /* ---- checksum (REQ_TYPE_CHECKSUM = 105; src/coprocessor/checksum.rs:59-114) ----
  * CRC-64/XZ per KV over key||value, XOR-folded (order-independent). */

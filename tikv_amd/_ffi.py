@@ -168,6 +168,12 @@ def load_lib():
     lib.copr_engine_narrow_launches.argtypes = [C.c_void_p]
     lib.copr_engine_narrow_builds.restype = C.c_uint64
     lib.copr_engine_narrow_builds.argtypes = [C.c_void_p]
+    lib.copr_engine_topn_multi_runs.restype = C.c_uint64
+    lib.copr_engine_topn_multi_runs.argtypes = [C.c_void_p]
+    lib.copr_engine_topn_last_kept.restype = C.c_uint64
+    lib.copr_engine_topn_last_kept.argtypes = [C.c_void_p]
+    lib.copr_engine_topn_last_candidates.restype = C.c_uint64
+    lib.copr_engine_topn_last_candidates.argtypes = [C.c_void_p]
     lib.copr_checksum.restype = C.c_int
     lib.copr_checksum.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32,
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),

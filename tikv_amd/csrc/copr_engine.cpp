@@ -101,6 +101,18 @@ extern "C" uint64_t copr_engine_narrow_builds(const copr_engine *eng) {
   return eng ? eng->narrow_builds : 0;
 }
 
+extern "C" uint64_t copr_engine_topn_multi_runs(const copr_engine *eng) {
+  return eng ? eng->topn_multi_runs : 0;
+}
+
+extern "C" uint64_t copr_engine_topn_last_kept(const copr_engine *eng) {
+  return eng ? eng->topn_last_kept : 0;
+}
+
+extern "C" uint64_t copr_engine_topn_last_candidates(const copr_engine *eng) {
+  return eng ? eng->topn_last_candidates : 0;
+}
+
 /* ---------------- region ---------------- */
 extern "C" copr_status copr_region_create(copr_engine *eng,
                                           const uint8_t *keys, const uint64_t *key_offs,
@@ -783,11 +795,15 @@ struct HostPlan {
   bool simple_as_stream = false;   /* simple agg with FIRST: one-run stream */
   bool hash_sorted = false;        /* FastHash + FIRST: sorted pipeline */
   CoprFieldType group_ft{};
-  /* TopN (top_n_executor.rs): single int order-by column */
+  /* TopN (top_n_executor.rs): int order-by columns. One order-by
+     expression: topn_off / topn_desc and dev_topn_select. Several (DESIGN
+     §9f): topn_multi with the distinct keys in topn_keys. */
   bool has_topn = false;
   uint64_t topn_n = 0;
   int topn_desc = 0;
   int topn_off = -1;
+  bool topn_multi = false;
+  std::vector<copr::TopnKey> topn_keys;
   int dec2_col_offset = -1;
   int filter2_col_offset = -1;
   uint64_t limit = UINT64_MAX;
@@ -1367,8 +1383,64 @@ static copr_status build_plan(const CoprDagRequest *req, HostPlan *pl) {
         break;
       case COPR_EXEC_TOPN: {
         if (pl->has_topn) return SET_ERR(COPR_ERR_UNSUPPORTED, "one TopN supported");
-        if (ex.n_order_by != 1)
+        if (ex.n_order_by == 0)
           return SET_ERR(COPR_ERR_UNSUPPORTED, "one order-by expression supported");
+        if (ex.n_order_by > 1) {
+          /* several keys: each a COLUMN_REF to an int non-handle column of a
+             table scan; a column that repeats cannot change the order after
+             its first occurrence and is dropped */
+          if (ex.n_order_by > COPR_TOPN_MAX_KEYS)
+            return SET_ERR(COPR_ERR_UNSUPPORTED,
+                           "multi-key TopN: at most 4 order-by expressions");
+          if (sp.index_mode)
+            return SET_ERR(COPR_ERR_UNSUPPORTED,
+                           "multi-key TopN over an index scan not yet native");
+          for (uint32_t k = 0; k < ex.n_order_by; k++) {
+            const CoprExpr &ke = ex.order_by[k];
+            if (ke.n_nodes != 1 || ke.nodes[0].kind != COPR_EXPR_COLUMN_REF)
+              return SET_ERR(COPR_ERR_UNSUPPORTED,
+                             "multi-key TopN: order-by must be a column");
+            size_t koff = (size_t)ke.nodes[0].i64_val;
+            if (koff >= pl->cols.size())
+              return SET_ERR(COPR_ERR_INVALID_REQUEST, "bad order-by offset");
+            const CoprColumnInfo &kc = pl->cols[koff];
+            if (kc.pk_handle)
+              return SET_ERR(COPR_ERR_UNSUPPORTED,
+                             "multi-key TopN: handle column as order key "
+                             "not yet native");
+            if (!et_int(kc.ft.tp))
+              return SET_ERR(COPR_ERR_UNSUPPORTED,
+                             "multi-key TopN: order-by type not yet native");
+            bool repeat = false;
+            for (const copr::TopnKey &pk : pl->topn_keys)
+              repeat |= pk.col_off == (int32_t)koff;
+            if (repeat) continue;
+            copr::TopnKey tk{};
+            tk.col_id = kc.column_id;
+            tk.col_off = (int32_t)koff;
+            tk.uns = (kc.ft.flag & COPR_FLAG_UNSIGNED) ? 1 : 0;
+            tk.desc = (ex.order_desc && ex.order_desc[k] != 0) ? 1 : 0;
+            /* absent cell: the scan's default fill, else NULL */
+            tk.missing_null = 1;
+            if (kc.default_val && kc.default_val_len) {
+              int64_t dv;
+              int r = host_decode_int_datum(kc.default_val, kc.default_val_len, &dv);
+              if (r < 0) return SET_ERR(COPR_ERR_INVALID_REQUEST, "bad default");
+              tk.missing_null = r == 1 ? 1 : 0;
+              tk.missing_val = dv;
+            }
+            pl->topn_keys.push_back(tk);
+          }
+          pl->has_topn = true;
+          pl->topn_multi = true;
+          pl->topn_off = pl->topn_keys[0].col_off;
+          pl->topn_n = ex.limit;
+          pl->topn_desc = pl->topn_keys[0].desc;
+          /* the extract pass (keep flags) parses the group slot: key 0 */
+          sp.group_col_id = pl->topn_keys[0].col_id;
+          sp.group_col_unsigned = pl->topn_keys[0].uns;
+          break;
+        }
         const CoprExpr &oe = ex.order_by[0];
         if (oe.n_nodes != 1 || oe.nodes[0].kind != COPR_EXPR_COLUMN_REF)
           return SET_ERR(COPR_ERR_UNSUPPORTED, "order-by must be a column");
@@ -1397,6 +1469,10 @@ static copr_status build_plan(const CoprDagRequest *req, HostPlan *pl) {
 
   if (agg && pl->has_topn)
     return SET_ERR(COPR_ERR_UNSUPPORTED, "TopN with aggregation unsupported");
+  if (pl->topn_multi && (sp.rpn_on || sp.n_xcap))
+    return SET_ERR(COPR_ERR_UNSUPPORTED,
+                   "multi-key TopN supports cmp(col,const) predicates only "
+                   "(no RPN or capture-channel predicates)");
   if (!agg) {
     if (sp.index_mode && sp.rpn_on)
       return SET_ERR(COPR_ERR_UNSUPPORTED,
@@ -2143,8 +2219,24 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
     pick_tiling(r->dev, &sp, /*force_nopipe=*/true);
     uint64_t take_n = pl.topn_n < pl.limit ? pl.topn_n : pl.limit;
     std::vector<uint32_t> winners;
-    int rc = dev_topn_select(sp, r->dev, take_n, pl.topn_desc, eng->stream,
-                             &winners);
+    /* multi-key: the winners' decoded key values, one list per key */
+    std::vector<int64_t> key_vals[COPR_TOPN_MAX_KEYS];
+    std::vector<uint8_t> key_nulls[COPR_TOPN_MAX_KEYS];
+    int rc;
+    if (pl.topn_multi) {
+      uint64_t kept = 0, cands = 0;
+      rc = dev_topn_multi_select(sp, r->dev, take_n, pl.topn_keys.data(),
+                                 (int)pl.topn_keys.size(), eng->stream,
+                                 &winners, key_vals, key_nulls, &kept, &cands);
+      if (rc == 0) {
+        eng->topn_multi_runs++;
+        eng->topn_last_kept = kept;
+        eng->topn_last_candidates = cands;
+      }
+    } else {
+      rc = dev_topn_select(sp, r->dev, take_n, pl.topn_desc, eng->stream,
+                           &winners);
+    }
     if (rc == -3) return SET_ERR(COPR_ERR_STORAGE, "row parse error on device");
     if (rc == -2) return SET_ERR(COPR_ERR_OOM, "topn temp alloc");
     if (rc) return SET_ERR(COPR_ERR_INTERNAL, "topn selection failed");
@@ -2204,13 +2296,47 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
     preq.div_precision_increment = req->div_precision_increment;
     copr_region *rp = &tmp;
     preq.encode_type = 0;                 /* post-encode below if chunked */
-    eng->dec_col_off = pl.topn_off;
-    eng->dec2_col_off =
-        (pl.sp.has_filter && pl.filter_col_offset >= 0 &&
-         pl.filter_col_offset != pl.topn_off) ? pl.filter_col_offset : -1;
+    if (pl.topn_multi) {
+      /* every order column is emitted decoded from the key values the
+         selection already produced; the two decode slots stay free for the
+         int predicate columns that are not order columns. A Real predicate
+         column needs none: its decoded datum equals its raw one. */
+      auto is_key = [&](int off) {
+        for (const copr::TopnKey &k : pl.topn_keys)
+          if (k.col_off == off) return true;
+        return false;
+      };
+      int d1 = -1, d2 = -1;
+      if (pl.sp.has_filter && !pl.sp.filter_is_real &&
+          pl.filter_col_offset >= 0 && !is_key(pl.filter_col_offset))
+        d1 = pl.filter_col_offset;
+      if (pl.sp.filter2_on && !pl.sp.filter2_is_real &&
+          pl.filter2_col_offset >= 0 && !is_key(pl.filter2_col_offset) &&
+          pl.filter2_col_offset != d1) {
+        if (d1 < 0) d1 = pl.filter2_col_offset;
+        else d2 = pl.filter2_col_offset;
+      }
+      eng->dec_col_off = d1;
+      eng->dec2_col_off = d2;
+      eng->topn_dec.clear();
+      for (size_t k = 0; k < pl.topn_keys.size(); k++) {
+        copr_engine::DecOverride ov;
+        ov.col_off = pl.topn_keys[k].col_off;
+        ov.uns = pl.topn_keys[k].uns != 0;
+        ov.vals = std::move(key_vals[k]);
+        ov.nulls = std::move(key_nulls[k]);
+        eng->topn_dec.push_back(std::move(ov));
+      }
+    } else {
+      eng->dec_col_off = pl.topn_off;
+      eng->dec2_col_off =
+          (pl.sp.has_filter && pl.filter_col_offset >= 0 &&
+           pl.filter_col_offset != pl.topn_off) ? pl.filter_col_offset : -1;
+    }
     copr_status st2 = copr_dag_run(eng, &preq, &rp, 1, out);
     eng->dec_col_off = -1;
     eng->dec2_col_off = -1;
+    eng->topn_dec.clear();
     free_sub();
     if (st2 == COPR_OK && req->encode_type == 1) {
       std::vector<uint8_t> dat(out->data, out->data + out->data_len);
@@ -2953,6 +3079,11 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         }
       }
       std::vector<uint8_t> rowbuf;
+      auto dec_override = [&](int off) -> const copr_engine::DecOverride * {
+        for (const copr_engine::DecOverride &ov : eng->topn_dec)
+          if (ov.col_off == off) return &ov;
+        return nullptr;
+      };
       for (uint64_t i = 0; i < scan_end && n_rows_out < pl.limit; i++) {
         if (!h_keep[i]) continue;
         const uint8_t *vbase = nullptr;
@@ -2970,6 +3101,14 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
           if (pl.sp.out_is_handle[off]) {
             enc_datum_int(&resp, h_handles[i],
                           (pl.cols[off].ft.flag & COPR_FLAG_UNSIGNED) != 0);
+            continue;
+          }
+          if (const copr_engine::DecOverride *ov = dec_override((int)off)) {
+            /* multi-key TopN order column: decoded by the order expression */
+            if (i >= ov->vals.size())
+              return SET_ERR(COPR_ERR_INTERNAL, "TopN key override short");
+            if (ov->nulls[i]) resp.push_back(0);
+            else enc_datum_int(&resp, ov->vals[i], ov->uns);
             continue;
           }
           if ((int)off == pl.dec2_col_offset && pl.sp.dec2_col_id) {

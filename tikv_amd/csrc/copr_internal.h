@@ -9,6 +9,7 @@
 
 #include "../../include/copr_types.h"   /* scalar sig / tp enums */
 #include "plane_fold.h"                  /* CMP_*, PlaneFcArgs, NarrowFcArgs */
+#include "topn_keys.h"                   /* TopnKey, order-key transform, cut */
 
 namespace copr {
 
@@ -388,6 +389,26 @@ int dev_stream_agg(const ScanPlan &plan, const DevRegion &rgn, void *stream,
 int dev_topn_select(const ScanPlan &plan, const DevRegion &rgn,
                     uint64_t topn_n, int desc, void *stream,
                     std::vector<uint32_t> *winners);
+/* multi-key TopN (topn_multi.hip). keys[0..n_keys) are distinct
+ * int columns. On 0: winners = source-row ids in output order, key_vals /
+ * key_nulls[k] = key k's decoded value / NULL flag per winner, *kept = rows
+ * the filters keep (m), *cands = rows that reached the secondary keys (c).
+ * -1 internal, -2 oom, -3 row parse error. */
+int dev_topn_multi_select(const ScanPlan &plan, const DevRegion &rgn,
+                          uint64_t take, const TopnKey *keys, int n_keys,
+                          void *stream, std::vector<uint32_t> *winners,
+                          std::vector<int64_t> *key_vals /*[n_keys]*/,
+                          std::vector<uint8_t> *key_nulls /*[n_keys]*/,
+                          uint64_t *kept, uint64_t *cands);
+/* kernels.hip halves of it: the scan path's keep flags, and one order key
+ * for a list of rows */
+int dev_topn_keep_flags(const ScanPlan &plan, const DevRegion &rgn,
+                        uint8_t *st, int64_t *gkey, unsigned int *d_err,
+                        void *stream);
+int dev_topn_keys_launch(const DevRegion &rgn, const uint32_t *d_rows,
+                         uint64_t cnt, const TopnKey &key,
+                         unsigned long long *d_u, uint8_t *d_rank,
+                         unsigned int *d_err, void *stream);
 /* fill keys[] with the EMPTY sentinel (INT64_MIN) */
 void dev_fill_keys(long long *keys, uint64_t n, void *stream);
 int dev_ht_compact(const HashAggTable &ht, uint32_t tsize, int n_aggs,
@@ -447,6 +468,21 @@ struct copr_engine {
      filter column when distinct from the order column. */
   int dec_col_off = -1;
   int dec2_col_off = -1;
+  /* multi-key TopN sub-region project: output columns whose
+     datum the host assembly takes from here instead of the row, in decoded
+     form; vals / nulls are indexed by sub-region row. Empty outside that
+     call: cleared on every exit path, like dec_col_off. */
+  struct DecOverride {
+    int col_off;
+    bool uns;
+    std::vector<int64_t> vals;
+    std::vector<uint8_t> nulls;
+  };
+  std::vector<DecOverride> topn_dec;
+  /* copr_engine_topn_multi_runs / _last_kept / _last_candidates */
+  uint64_t topn_multi_runs = 0;
+  uint64_t topn_last_kept = 0;
+  uint64_t topn_last_candidates = 0;
   /* RCCL communicator state (copr_comm.cpp); null until copr_comm_create */
   void *comm_state = nullptr;
   /* hash-agg table cache: the per-request hipMalloc/hipFree set measured

@@ -6184,6 +6184,72 @@ int dev_topn_select(const ScanPlan &plan, const DevRegion &rgn,
   return 0;
 }
 
+/* ---- multi-key TopN: the two steps that need this file's row
+ * parsers; the pipeline itself is topn_multi.hip ---- */
+
+/* keep decision of the scan path for every row: st[i] != 0 = kept. gkey is
+ * [n] scratch for the extract pass's group slot (the plan's group column is
+ * order key 0). */
+int dev_topn_keep_flags(const ScanPlan &plan, const DevRegion &rgn,
+                        uint8_t *st, int64_t *gkey, unsigned int *d_err,
+                        void *stream) {
+  ExtractOut eo{st, gkey, nullptr, nullptr, nullptr, nullptr, nullptr};
+  ScanPlan p0 = plan;
+  p0.n_aggs = 0;
+  return extract_launch(p0, rgn, eo, d_err, (hipStream_t)stream);
+}
+
+/* One order key for cnt rows named by rows[]: locate the cell as the plane
+ * builder does (directory byte, or a row walk without one; row-v2 through
+ * d_v2_find / d_v2_int with the request's signedness), fill an absent cell
+ * from the column default, and write topn_key_encode's (rank, u). */
+__global__ void __launch_bounds__(256)
+k_topn_keys(const uint8_t *__restrict__ vals,
+            const uint64_t *__restrict__ val_offs,
+            const uint8_t *__restrict__ dirp,
+            const uint32_t *__restrict__ rows, uint64_t cnt, TopnKey key,
+            unsigned long long *__restrict__ u_out,
+            uint8_t *__restrict__ rank_out, unsigned int *__restrict__ err) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  bool any_err = false;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt;
+       i += stride) {
+    ChanRes cr = d_plane_resolve(dirp, rows[i], key.col_id, key.uns != 0, 0,
+                                 vals, val_offs);
+    any_err |= (cr.fl & CH_ERR) != 0;
+    bool is_null;
+    int64_t v;
+    if (cr.fl & CH_FOUND) {
+      is_null = (cr.fl & CH_NULL) != 0;
+      v = cr.v;
+    } else {
+      is_null = key.missing_null != 0;
+      v = key.missing_val;
+    }
+    uint8_t rk;
+    unsigned long long u;
+    topn_key_encode(v, is_null, key.uns != 0, key.desc != 0, &rk, &u);
+    u_out[i] = u;
+    rank_out[i] = rk;
+  }
+  if (any_err) atomicOr(err, 1u);
+}
+
+int dev_topn_keys_launch(const DevRegion &rgn, const uint32_t *d_rows,
+                         uint64_t cnt, const TopnKey &key,
+                         unsigned long long *d_u, uint8_t *d_rank,
+                         unsigned int *d_err, void *stream) {
+  if (!cnt) return 0;
+  const uint8_t *dirp =
+      (rgn.d_celldir && key.col_id >= 1 && key.col_id <= 16)
+          ? rgn.d_celldir + (uint64_t)(key.col_id - 1) * rgn.n_kv : nullptr;
+  uint32_t grid = (uint32_t)min((cnt + 255) / 256, (uint64_t)16384);
+  hipLaunchKernelGGL(k_topn_keys, dim3(grid), dim3(256), 0,
+                     (hipStream_t)stream, rgn.d_vals, rgn.d_val_offs, dirp,
+                     d_rows, cnt, key, d_u, d_rank, d_err);
+  return (int)hipGetLastError();
+}
+
 
 
 /* compact a global hash table's occupied slots (keys + accumulator rows)

@@ -559,6 +559,15 @@ class Engine:
         return (self._lib.copr_engine_narrow_launches(self._h),
                 self._lib.copr_engine_narrow_builds(self._h))
 
+    def topn_stats(self):
+        """(runs, kept, candidates): TopN requests served by the multi-key
+        pipeline since the engine was created, and for the last of them the
+        rows its filters kept and the rows that passed the primary-key
+        candidate cut. Single-key TopN moves none of the three."""
+        return (self._lib.copr_engine_topn_multi_runs(self._h),
+                self._lib.copr_engine_topn_last_kept(self._h),
+                self._lib.copr_engine_topn_last_candidates(self._h))
+
     def close(self):
         if self._h:
             self._lib.copr_engine_destroy(self._h)
