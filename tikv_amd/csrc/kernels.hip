@@ -1220,74 +1220,585 @@ __device__ static inline void d_simple_epilogue(
   }
 }
 
+/* ---------------- row collector shared by the row-scan kernels ------------
+ * What one row yields for a plan: the filter, filter2 and group channels
+ * here, and one AggColView per aggregate in an array of the caller's.
+ * grp_off is the group cell's offset within the row (GRP_RAW collection
+ * only). The array is not a member: the 8-aggregate instances index it
+ * dynamically, which keeps it in scratch, and as a member it would take these
+ * scalars there with it. */
+struct RowVals {
+  bool filt_found, filt_null; int64_t filt_v;
+  bool f2_found, f2_null; int64_t f2_v;
+  bool grp_found, grp_null; int64_t grp_v;
+  uint32_t grp_off;
+};
+
+__device__ static inline void d_cell_to_col(const CellView &cell,
+                                            AggColView *c, bool *parse_ok) {
+  c->found = true;
+  c->null = cell.is_null;
+  c->iv = cell.ival;
+  c->has_dec = cell.has_dec;
+  c->dsc = cell.dscaled; c->dfr = cell.dfrac;
+  c->dwide = cell.dwide; c->dwrem = cell.dwide_rem;
+  if (!cell.is_null && !cell.has_int && !cell.has_real && !cell.has_dec &&
+      !cell.dwide)
+    *parse_ok = false;
+}
+
+__device__ static inline void d_cell_to_filter(const CellView &cell,
+                                               bool want_real, bool *found,
+                                               bool *null, int64_t *v,
+                                               bool *parse_ok) {
+  *found = true;
+  if (cell.is_null) *null = true;
+  else if (want_real ? cell.has_real : cell.has_int) *v = cell.ival;
+  else *parse_ok = false;
+}
+
+/* group cell: an int, or under GRP_RAW with grp_raw set just its offset (the
+   caller takes the raw span from there) */
+template <bool GRP_RAW>
+__device__ static inline void d_cell_to_group(const CellView &cell,
+                                              uint32_t cell_off, bool grp_raw,
+                                              RowVals &rv,
+                                              bool *parse_ok) {
+  rv.grp_found = true;
+  if (cell.is_null) rv.grp_null = true;
+  else if (GRP_RAW && grp_raw) rv.grp_off = cell_off;
+  else if (cell.has_int) rv.grp_v = cell.ival;
+  else *parse_ok = false;
+}
+
+/* Fills rv for the row (vp, vlen) and returns parse_ok: index-key walk in
+ * index mode; else one direct next_cell per needed column when the cell
+ * directory places them all; else the row-v2 lookup or the row-v1 walk, which
+ * stops once every needed column was seen. The group column is looked up only
+ * when IS_HASH. dload(slab, col_id) yields the row's directory byte for a
+ * column. GRP_RAW (k_scan_extract) and grp_raw: the group cell is wanted as
+ * raw bytes, see d_cell_to_group; row-v2 rows then leave the group channel to
+ * the caller. Reusing the parsed group value for an aggregate over the group
+ * column is the aggregate kernels' (!GRP_RAW) directory branch only. */
+template <int NAGGS, bool IS_HASH, bool GRP_RAW, typename DirLoad>
+__device__ static inline __attribute__((always_inline)) bool d_row_collect(
+    const ScanPlan &plan, const uint8_t *vp, uint32_t vlen, uint64_t my_row,
+    DirLoad dload, RowVals &rv, AggColView (&cols)[NAGGS],
+    bool grp_raw = false) {
+  bool parse_ok = true;
+  rv.filt_found = false; rv.filt_null = false; rv.filt_v = 0;
+  rv.f2_found = false; rv.f2_null = false; rv.f2_v = 0;
+  rv.grp_found = false; rv.grp_null = false; rv.grp_v = 0;
+  rv.grp_off = 0;
+  #pragma unroll
+  for (int a = 0; a < NAGGS; a++) cols[a] = {false, false, false, 0, 0, 0, nullptr, 0};
+
+  if (plan.index_mode) {
+    int64_t hval = 0; bool hfound = false;
+    parse_ok = d_index_collect<NAGGS, IS_HASH>(plan, vp, vlen, my_row,
+                                               &rv.filt_found, &rv.filt_null,
+                                               &rv.filt_v, &rv.grp_found,
+                                               &rv.grp_null, &rv.grp_v, cols,
+                                               &hval, &hfound);
+  } else if (!(vlen == 0 || (vlen == 1 && vp[0] == 0))) {
+  /* directory fast path: one direct next_cell per needed column instead of a
+     sequential walk over every cell */
+  bool dir_done = false;
+  if (plan.celldir && vp[0] != 128) {
+    uint32_t d_f = 0xFFu, d_f2 = 0xFFu, d_g = 0xFFu, d_a[NAGGS];
+    if (plan.has_filter) d_f = dload(plan.dirslab_f, plan.filter_col_id);
+    if (plan.filter2_on) d_f2 = dload(plan.dirslab_f2, plan.filter2_col_id);
+    if (IS_HASH) d_g = dload(plan.dirslab_g, plan.group_col_id);
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++) {
+      d_a[a] = 0xFFu;
+      if (plan.aggs[a].kind != DAGG_COUNT_ROWS)
+        d_a[a] = dload(plan.dirslab_a[a], plan.aggs[a].col_id);
+    }
+    bool seq = (d_f == 0xFEu) | (d_f2 == 0xFEu) | (d_g == 0xFEu);
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++) seq |= (d_a[a] == 0xFEu);
+    if (!seq) {
+      dir_done = true;
+      int64_t cid; uint32_t coff; CellView cell; uint32_t pos;
+      if (plan.has_filter && d_f != 0xFFu) {
+        pos = d_f;
+        if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
+            cid == plan.filter_col_id)
+          d_cell_to_filter(cell, plan.filter_is_real, &rv.filt_found,
+                           &rv.filt_null, &rv.filt_v, &parse_ok);
+        else parse_ok = false;
+      }
+      if (plan.filter2_on && d_f2 != 0xFFu) {
+        pos = d_f2;
+        if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
+            cid == plan.filter2_col_id)
+          d_cell_to_filter(cell, plan.filter2_is_real, &rv.f2_found,
+                           &rv.f2_null, &rv.f2_v, &parse_ok);
+        else parse_ok = false;
+      }
+      if (IS_HASH && d_g != 0xFFu) {
+        pos = d_g;
+        if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
+            cid == plan.group_col_id)
+          d_cell_to_group<GRP_RAW>(cell, coff, grp_raw, rv, &parse_ok);
+        else parse_ok = false;
+      }
+      #pragma unroll
+      for (int a = 0; a < NAGGS; a++) {
+        if (plan.aggs[a].kind == DAGG_COUNT_ROWS || d_a[a] == 0xFFu)
+          continue;
+        if (IS_HASH && !GRP_RAW && rv.grp_found && !rv.grp_null && parse_ok &&
+            plan.aggs[a].col_id == plan.group_col_id &&
+            plan.aggs[a].kind != DAGG_SUM_DEC &&
+            plan.aggs[a].kind != DAGG_SUM_REAL) {
+          /* agg over the GROUP column: reuse the parsed int value
+             (avg/sum BY the same column parses the cell once) */
+          cols[a].found = true;
+          cols[a].null = false;
+          cols[a].iv = rv.grp_v;
+          continue;
+        }
+        if (IS_HASH && !GRP_RAW && rv.grp_found && rv.grp_null && parse_ok &&
+            plan.aggs[a].col_id == plan.group_col_id) {
+          cols[a].found = true;
+          cols[a].null = true;
+          continue;
+        }
+        pos = d_a[a];
+        if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
+            cid == plan.aggs[a].col_id)
+          d_cell_to_col(cell, &cols[a], &parse_ok);
+        else parse_ok = false;
+      }
+    }
+  }
+  if (dir_done) {
+  } else if (vp[0] == 128) {   /* row v2 */
+    parse_ok = d_v2_collect<NAGGS, IS_HASH>(
+        plan, vp, vlen, &rv.filt_found, &rv.filt_null, &rv.filt_v,
+        &rv.grp_found, &rv.grp_null, &rv.grp_v, cols, !(GRP_RAW && grp_raw),
+        &rv.f2_found, &rv.f2_null, &rv.f2_v);
+  } else {
+  int needed = (plan.has_filter ? 1 : 0) + (plan.filter2_on ? 1 : 0) + (IS_HASH ? 1 : 0);
+  #pragma unroll
+  for (int a = 0; a < NAGGS; a++)
+    if (plan.aggs[a].kind != DAGG_COUNT_ROWS) needed++;
+  int found = 0;
+  uint32_t pos = 0;
+  while (pos < vlen) {
+    int64_t cell_id;
+    uint32_t cell_off;
+    CellView cell;
+    if (!next_cell(vp, vlen, &pos, &cell_id, &cell_off, &cell)) {
+      parse_ok = false;
+      break;
+    }
+    if (plan.has_filter && !rv.filt_found && cell_id == plan.filter_col_id) {
+      d_cell_to_filter(cell, plan.filter_is_real, &rv.filt_found,
+                       &rv.filt_null, &rv.filt_v, &parse_ok);
+      found++;
+    }
+    if (plan.filter2_on && !rv.f2_found && cell_id == plan.filter2_col_id) {
+      d_cell_to_filter(cell, plan.filter2_is_real, &rv.f2_found, &rv.f2_null,
+                       &rv.f2_v, &parse_ok);
+      found++;
+    }
+    if (IS_HASH && !rv.grp_found && cell_id == plan.group_col_id) {
+      d_cell_to_group<GRP_RAW>(cell, cell_off, grp_raw, rv, &parse_ok);
+      found++;
+    }
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++) {
+      if (plan.aggs[a].kind == DAGG_COUNT_ROWS || cols[a].found) continue;
+      if (cell_id == plan.aggs[a].col_id) {
+        d_cell_to_col(cell, &cols[a], &parse_ok);
+        found++;
+      }
+    }
+    if (found >= needed) break;
+  }
+  }  /* v1 walk */
+  }  /* non-empty row */
+  return parse_ok;
+}
+
+/* ---------------- accumulate step shared by the aggregate kernels ---------
+ * These are the only implementation of group-slot selection, the
+ * per-aggregate update and the LDS-table init and flush: k_scan_agg,
+ * k_scan_agg_pipe and k_plane_hash all call them, so a group lands in the
+ * same slot with the same accumulator bits whichever kernel saw the row.
+ * Stride rule: every accumulator array (ht.accs, ht.ext, ht.reserved,
+ * ht.rsvd_ext and the LDS table) is laid out with the plan's n_aggs, never
+ * with the NAGGS a kernel instance unrolls to; na = min(n_aggs, NAGGS) and
+ * per-aggregate loops skip a >= na. */
+
+/* what the wide-decimal pre-pass and the rescale need to know about one
+   sum(decimal) input */
+struct DecIn { bool live /* found, not NULL */, wide, has_dec; int64_t sc; int32_t frac; };
+
+/* conservative wide-decimal pre-pass: a row that may need a 256-bit add must
+   take a GLOBAL slot (the LDS table is 128-bit). dec_of(a) -> DecIn. */
+template <int NAGGS, typename DecOf>
+__device__ static inline __attribute__((always_inline)) bool d_row_wide(
+    const ScanPlan &plan, DecOf dec_of) {
+  bool row_wide = false;
+  #pragma unroll
+  for (int a = 0; a < NAGGS; a++) {
+    if (plan.aggs[a].kind != DAGG_SUM_DEC) continue;
+    const DecIn di = dec_of(a);
+    if (!di.live) continue;
+    if (di.wide) { row_wide = true; continue; }
+    if (!di.has_dec) continue;
+    int d = plan.aggs[a].target_frac - di.frac;
+    if (d > 18) { row_wide = true; continue; }
+    if (d > 0) {
+      int64_t lim = (int64_t)(0x7FFFFFFFFFFFFFFFll);
+      for (int t = 0; t < d; t++) lim /= 10;
+      if (di.sc > lim || di.sc < -lim) row_wide = true;
+    }
+  }
+  return row_wide;
+}
+
+/* sum(decimal): scale sv (frac digits) to target_frac, 0..38 digits. A value
+   that fits an i64 comes back in *v, else in *vw with *dec_wide (the 256-bit
+   path). False = frac past the target, or a scaled value past 38 digits. */
+__device__ static inline bool d_dec_rescale(__int128 sv, int32_t frac,
+                                            int32_t target_frac, int64_t *v,
+                                            __int128 *vw, bool *dec_wide) {
+  int d = target_frac - frac;
+  if (d < 0 || d > 38) return false;
+  const __int128 LIM =
+      (__int128)(((unsigned __int128)~(unsigned __int128)0) >> 1) / 10;
+  for (int t = 0; t < d; t++) {
+    if (sv > LIM || sv < -LIM) return false;
+    sv *= 10;
+  }
+  if (sv >= (__int128)INT64_MIN && sv <= (__int128)INT64_MAX) {
+    *v = (int64_t)sv;
+  } else {
+    *vw = sv;
+    *dec_wide = true;
+  }
+  return true;
+}
+
+/* one aggregate's value from its collected column: false = no contribution
+   (capture-only channel, NULL or absent cell, or a decimal error, which sets
+   *err) */
+__device__ static inline bool d_agg_value(const DevAggSpec &sp,
+                                          const AggColView &c, int64_t *v,
+                                          __int128 *vw, bool *dec_wide,
+                                          bool *err) {
+  if (sp.kind == DAGG_XCAP) return false;          /* capture-only channel */
+  if (sp.kind == DAGG_COUNT_ROWS) return true;
+  if (!c.found || c.null) return false;
+  if (sp.kind == DAGG_COUNT_COL) return true;
+  if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_REAL ||
+      d_is_fold(sp.kind)) {
+    *v = c.iv;
+    return true;
+  }
+  /* SUM_DEC: values to 38 digits via the i128 parse; a scaled value past
+     i64 goes to the 256-bit path */
+  __int128 sv = 0;
+  int32_t fr = 0;
+  bool okd = true;
+  if (c.has_dec) {
+    sv = c.dsc;
+    fr = c.dfr;
+  } else if (c.dwide) {
+    if (!d_decimal_scaled128(c.dwide, c.dwrem, &sv, &fr)) okd = false;
+  } else {
+    okd = false;
+  }
+  if (!okd || !d_dec_rescale(sv, fr, sp.target_frac, v, vw, dec_wide)) {
+    *err = true;                                   /* loud */
+    return false;
+  }
+  return true;
+}
+
+/* PLANE_KINDS = the caller's plans hold only what hash_plane_plan_ok admits:
+   count, sum(int), sum(decimal), max(int), min(int). k_plane_hash passes
+   true, and the chain of kind tests in its row loop stays as short as those
+   kinds need; each test of a by-value plan field costs a spilled-SGPR
+   reload there. The arithmetic per kind is the same either way. */
+template <bool PLANE_KINDS>
+__device__ static inline bool d_fold_kind(int32_t kind) {
+  return PLANE_KINDS ? (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT)
+                     : d_is_fold(kind);
+}
+
+/* fold kinds on an accumulator word: b = the d_fold_xform'd value */
+template <bool PLANE_KINDS>
+__device__ static inline void d_fold_atomic(int32_t kind,
+                                            unsigned long long *w,
+                                            unsigned long long b) {
+  if (PLANE_KINDS) atomicMax(w, b);
+  else if (d_is_xor(kind)) atomicXor(w, b);
+  else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT ||
+           kind == DAGG_MAX_REAL || kind == DAGG_MIN_REAL)
+    atomicMax(w, b);
+  else atomicOr(w, b);
+}
+
+struct HashSlot { SimpleAggAcc *acc; unsigned long long *ext; };
+
+__device__ static inline uint64_t d_group_hash(int64_t key) {
+  uint64_t h = (uint64_t)key * 0x9E3779B97F4A7C15ull;
+  return h ^ (h >> 29);
+}
+
+/* find-or-claim key's slot in the global open-addressed table; a full table
+   raises ht.error[0] and returns a null acc (the host grows and retries) */
+__device__ static inline HashSlot d_hash_global_slot(const HashAggTable &ht,
+                                                     uint32_t table_size,
+                                                     uint32_t na,
+                                                     int64_t key) {
+  const unsigned long long EMPTY = 0x8000000000000000ull;
+  HashSlot hs{nullptr, nullptr};
+  uint32_t mask = table_size - 1u;
+  uint32_t slot = (uint32_t)(d_group_hash(key) & mask);
+  for (uint32_t probe = 0; ; probe++) {
+    if (probe > mask) { atomicOr(ht.error, 1u); break; }
+    unsigned long long curk =
+        atomicCAS((unsigned long long *)&ht.keys[slot], EMPTY,
+                  (unsigned long long)key);
+    if (curk == EMPTY) atomicAdd(ht.n_groups, 1ull);
+    if (curk == EMPTY || curk == (unsigned long long)key) {
+      hs.acc = ht.accs + (uint64_t)slot * na;
+      if (ht.ext) hs.ext = ht.ext + (uint64_t)slot * na * 2;
+      break;
+    }
+    slot = (slot + 1) & mask;
+  }
+  return hs;
+}
+
+/* one kept row's accumulator block: NULL/absent keys -> reserved[1],
+   INT64_MIN (the EMPTY sentinel) -> reserved[0], everything else the block's
+   LDS pre-aggregation table first (128-bit accumulators, so never for a row
+   that may need a 256-bit add) and the global table when that is full */
+__device__ static inline HashSlot d_hash_row_slot(
+    const HashAggTable &ht, uint32_t table_size, uint32_t na, bool grp_found,
+    bool grp_null, int64_t grp_v, bool row_wide, long long *lkeys,
+    SimpleAggAcc *laccs, uint32_t lslots) {
+  HashSlot hs{nullptr, nullptr};
+  if (!grp_found || grp_null) {
+    atomicAdd(&ht.rsvd_seen[1], 1ull);
+    hs.acc = ht.reserved + 1 * na;
+    if (ht.rsvd_ext) hs.ext = ht.rsvd_ext + 1 * na * 2;
+    return hs;
+  }
+  if (grp_v == (long long)0x8000000000000000ll) {
+    atomicAdd(&ht.rsvd_seen[0], 1ull);
+    hs.acc = ht.reserved;
+    if (ht.rsvd_ext) hs.ext = ht.rsvd_ext;
+    return hs;
+  }
+  if (lslots && !row_wide) {
+    const unsigned long long EMPTY = 0x8000000000000000ull;
+    uint32_t lmask = lslots - 1u;
+    uint32_t slot = (uint32_t)(d_group_hash(grp_v) & lmask);
+    for (uint32_t probe = 0; probe <= lmask / 2; probe++) {
+      unsigned long long curk =
+          atomicCAS((unsigned long long *)&lkeys[slot], EMPTY,
+                    (unsigned long long)grp_v);
+      if (curk == EMPTY || curk == (unsigned long long)grp_v) {
+        hs.acc = laccs + (uint64_t)slot * na;
+        return hs;
+      }
+      slot = (slot + 1) & lmask;
+    }
+  }
+  return d_hash_global_slot(ht, table_size, na, grp_v);
+}
+
+/* one aggregate's contribution to its accumulator (LDS or global; ext = the
+   two high limbs when the accumulator is 256-bit). A 256-bit accumulator
+   must see every add as i256: a narrow negative i128 add would not borrow
+   from the ext limbs. False = a wide value met a 128-bit accumulator. */
+template <bool PLANE_KINDS>
+__device__ static inline bool d_hash_update(const DevAggSpec &sp,
+                                            SimpleAggAcc *acc,
+                                            unsigned long long *ext,
+                                            int64_t v, __int128 vw,
+                                            bool dec_wide) {
+  atomicAdd(&acc->cnt, 1ull);
+  if (!PLANE_KINDS && sp.kind == DAGG_SUM_REAL) {
+    atomicAdd((double *)&acc->sum_lo, __longlong_as_double(v));
+  } else if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_DEC) {
+    if (ext)
+      atomic_add_i256(&acc->sum_lo, &acc->sum_hi, ext,
+                      dec_wide ? vw : (__int128)v);
+    else if (dec_wide)
+      return false;
+    else
+      atomic_add_i128(&acc->sum_lo, &acc->sum_hi, v);
+  } else if (d_fold_kind<PLANE_KINDS>(sp.kind)) {
+    d_fold_atomic<PLANE_KINDS>(sp.kind, &acc->sum_lo,
+                               d_fold_xform(sp.kind, v, sp.col_unsigned));
+  }
+  return true;
+}
+
+/* prologue: empty the block's LDS pre-aggregation table (lslots keys, then
+   lslots * n_aggs accumulators); the caller barriers */
+template <int NAGGS>
+__device__ static inline void d_hash_lds_init(const ScanPlan &plan,
+                                              long long *lkeys,
+                                              SimpleAggAcc *laccs,
+                                              uint32_t lslots) {
+  const uint32_t na = min((uint32_t)plan.n_aggs, (uint32_t)NAGGS);
+  for (uint32_t s = threadIdx.x; s < lslots; s += blockDim.x) {
+    lkeys[s] = (long long)0x8000000000000000ll;
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++)
+      if ((uint32_t)a < na) laccs[s * na + a] = SimpleAggAcc{0, 0, 0};
+  }
+}
+
+/* epilogue: merge the block's LDS pre-aggregation table into the global one */
+template <int NAGGS, bool PLANE_KINDS>
+__device__ static inline void d_hash_lds_flush(const ScanPlan &plan,
+                                               const HashAggTable &ht,
+                                               const long long *lkeys,
+                                               const SimpleAggAcc *laccs,
+                                               uint32_t lslots) {
+  const uint32_t na = min((uint32_t)plan.n_aggs, (uint32_t)NAGGS);
+  for (uint32_t s = threadIdx.x; s < lslots; s += blockDim.x) {
+    long long key = lkeys[s];
+    if (key == (long long)0x8000000000000000ll) continue;
+    HashSlot gs = d_hash_global_slot(ht, plan.table_size, na, key);
+    if (!gs.acc) continue;
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++) {
+      if ((uint32_t)a >= na) continue;
+      const SimpleAggAcc la = laccs[s * na + a];
+      const int32_t kind = plan.aggs[a].kind;
+      if (la.cnt) atomicAdd(&gs.acc[a].cnt, la.cnt);
+      if (d_fold_kind<PLANE_KINDS>(kind)) {
+        if (la.sum_lo)
+          d_fold_atomic<PLANE_KINDS>(kind, &gs.acc[a].sum_lo, la.sum_lo);
+        continue;
+      }
+      if (la.sum_lo | la.sum_hi) {
+        if (gs.ext) {
+          atomic_add_i256(&gs.acc[a].sum_lo, &gs.acc[a].sum_hi,
+                          gs.ext + a * 2,
+                          (__int128)(((unsigned __int128)la.sum_hi << 64) |
+                                     la.sum_lo));
+        } else {
+          unsigned long long old = atomicAdd(&gs.acc[a].sum_lo, la.sum_lo);
+          long long carry = (old + la.sum_lo < old) ? 1 : 0;
+          long long hi_add = (long long)la.sum_hi + carry;
+          if (hi_add) atomicAdd(&gs.acc[a].sum_hi, (unsigned long long)hi_add);
+        }
+      }
+    }
+  }
+}
+
+/* simple (ungrouped) aggregation: one contribution into the lane's partials,
+   folded by d_simple_epilogue. A wide decimal goes straight to the 256-bit
+   global accumulator; the per-lane i128 partial keeps only i64-fitting
+   values. False = a wide value and no ext buffers. */
+__device__ static inline bool d_simple_update(
+    const ScanPlan &plan, const DevAggSpec &sp, int a,
+    SimpleAggAcc *__restrict__ simple_acc, int64_t v, __int128 vw,
+    bool dec_wide, unsigned long long *l_cnt, unsigned long long *l_lo,
+    long long *l_hi) {
+  (*l_cnt)++;
+  if (sp.kind == DAGG_SUM_REAL) {
+    *l_lo = (unsigned long long)__double_as_longlong(
+        __longlong_as_double((long long)*l_lo) + __longlong_as_double(v));
+  } else if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_DEC) {
+    if (dec_wide) {
+      if (!plan.simple_ext) return false;
+      atomic_add_i256(&simple_acc[a].sum_lo, &simple_acc[a].sum_hi,
+                      plan.simple_ext + a * 2, vw);
+    } else {
+      unsigned long long old = *l_lo;
+      unsigned long long nv = old + (unsigned long long)v;
+      *l_hi += (nv < old ? 1 : 0) + (v < 0 ? -1 : 0);
+      *l_lo = nv;
+    }
+  } else if (d_is_fold(sp.kind)) {
+    unsigned long long b = d_fold_xform(sp.kind, v, sp.col_unsigned);
+    if (d_is_xor(sp.kind)) *l_lo ^= b;
+    else if (sp.kind == DAGG_MAX_INT || sp.kind == DAGG_MIN_INT ||
+             sp.kind == DAGG_MAX_REAL || sp.kind == DAGG_MIN_REAL)
+      *l_lo = *l_lo > b ? *l_lo : b;
+    else *l_lo |= b;
+  }
+  return true;
+}
+
+/* One collected row through the keep decision and into the accumulators: the
+ * hash table (IS_HASH) or the lane's simple partials. Returns true when the
+ * row raised the request's parse error (bad row, keep error, decimal error,
+ * wide value without ext buffers). */
+template <int NAGGS, bool IS_HASH>
+__device__ static inline __attribute__((always_inline)) bool d_row_accumulate(
+    const ScanPlan &plan, bool parse_ok, const RowVals &rv,
+    const AggColView (&cols)[NAGGS],
+    const HashAggTable &ht, long long *lkeys, SimpleAggAcc *laccs,
+    uint32_t lslots, SimpleAggAcc *__restrict__ simple_acc,
+    unsigned long long (&l_cnt)[NAGGS], unsigned long long (&l_lo)[NAGGS],
+    long long (&l_hi)[NAGGS]) {
+  int64_t xv0_ = 0, xv1_ = 0;
+  uint8_t xn0_ = 0, xn1_ = 0;
+  if (plan.n_xcap)
+    d_xcap_extract(plan, cols, &xv0_, &xn0_, &xv1_, &xn1_);
+  bool err = false;
+  if (!parse_ok) {
+    err = true;
+  } else if (d_keep2(plan, rv.filt_found, rv.filt_null, rv.filt_v,
+                     rv.f2_found, rv.f2_null, rv.f2_v, &err, xv0_, xn0_, xv1_,
+                     xn1_)) {               /* else dropped, or a keep error */
+  const uint32_t na = min((uint32_t)plan.n_aggs, (uint32_t)NAGGS);
+  HashSlot hs{nullptr, nullptr};
+  if (IS_HASH) {
+    const bool row_wide = d_row_wide<NAGGS>(plan, [&](int a) {
+      const AggColView &c = cols[a];
+      return DecIn{c.found && !c.null, c.dwide != nullptr, c.has_dec, c.dsc,
+                   c.dfr};
+    });
+    hs = d_hash_row_slot(ht, plan.table_size, na, rv.grp_found, rv.grp_null,
+                         rv.grp_v, row_wide, lkeys, laccs, lslots);
+  }
+  #pragma unroll
+  for (int a = 0; a < NAGGS; a++) {
+    if (IS_HASH && (uint32_t)a >= na) continue;
+    const DevAggSpec &sp = plan.aggs[a];
+    bool dec_wide = false;       /* value does not fit a scaled i64 */
+    __int128 vw = 0;
+    int64_t v = 0;
+    if (!d_agg_value(sp, cols[a], &v, &vw, &dec_wide, &err)) continue;
+    if (IS_HASH) {
+      if (hs.acc &&
+          !d_hash_update<false>(sp, hs.acc + a,
+                                hs.ext ? hs.ext + a * 2 : nullptr, v, vw,
+                                dec_wide))
+        err = true;                      /* no ext buffers: loud */
+    } else if (!d_simple_update(plan, sp, a, simple_acc, v, vw, dec_wide,
+                                &l_cnt[a], &l_lo[a], &l_hi[a])) {
+      err = true;
+    }
+  }
+  }
+  return err;
+}
+
 /* ---------------- fused scan + filter + aggregate ----------------
  * NAGGS is a compile-time bound so all per-row/per-lane state stays in
- * registers. IS_HASH selects grouped aggregation. NLOADS = staged uint4
- * loads per lane per tile (compile-time so the load batch is unconditional
- * and register-resident): the block software-pipelines tiles — while lanes
- * parse tile t from LDS, the loads for tile t+1 are already in flight into
- * registers (async-STAGE split, cdna_hip_programming G15). */
-
-struct TileInfo {
-  uint64_t row0, row1, gbase;
-  uint32_t shift, n16;
-};
-
-template <int NLOADS>
-__device__ static inline void tile_info(const uint64_t *__restrict__ val_offs,
-                                        uint64_t n_rows, uint32_t rpt,
-                                        uint64_t tile, TileInfo *ti) {
-  ti->row0 = tile * rpt;
-  ti->row1 = min(ti->row0 + rpt, n_rows);
-  uint64_t gb = val_offs[ti->row0];
-  uint64_t ge = val_offs[ti->row1];
-  uint64_t abase = gb & ~15ull;
-  ti->gbase = gb;
-  ti->shift = (uint32_t)(gb - abase);
-  ti->n16 = (uint32_t)(((ge - gb) + ti->shift + 15ull) >> 4);
-}
-
-/* the staging buffer is NLOADS NAMED uint4s (not an array): hipcc's
- * allocator spills a local array with a long live range to scratch even
- * with VGPR budget to spare */
-template <int NLOADS>
-struct StageRegs {
-  uint4 r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15;
-};
-
-#define STAGE_EACH(OP) \
-  OP(0) OP(1) OP(2) OP(3) OP(4) OP(5) OP(6) OP(7) \
-  OP(8) OP(9) OP(10) OP(11) OP(12) OP(13) OP(14) OP(15)
-
-template <int NLOADS>
-__device__ static inline void tile_load(const uint8_t *__restrict__ vals,
-                                        const TileInfo &ti, StageRegs<NLOADS> &R) {
-  const uint4 *gs = (const uint4 *)(vals + (ti.gbase & ~15ull));
-  uint32_t last = ti.n16 ? ti.n16 - 1u : 0u;
-  /* clamped, UNCONDITIONAL loads (a per-element branch makes hipcc wait
-     vmcnt(0) per element — §6 trap (c)); duplicates hit L2 */
-  #define COPR_LOADJ(J) \
-    if constexpr (J < NLOADS) \
-      R.r##J = gs[min(threadIdx.x + (uint32_t)J * THREADS, last)];
-  STAGE_EACH(COPR_LOADJ)
-  #undef COPR_LOADJ
-}
-
-template <int NLOADS>
-__device__ static inline void tile_store(uint8_t *lds, const TileInfo &ti,
-                                         const StageRegs<NLOADS> &R) {
-  uint4 *ld = (uint4 *)lds;
-  uint32_t last = ti.n16 ? ti.n16 - 1u : 0u;
-  /* clamped stores: the clamped duplicate rewrites the same element with
-     the same value */
-  #define COPR_STOREJ(J) \
-    if constexpr (J < NLOADS) \
-      ld[min(threadIdx.x + (uint32_t)J * THREADS, last)] = R.r##J;
-  STAGE_EACH(COPR_STOREJ)
-  #undef COPR_STOREJ
-}
-
-template <int NAGGS, bool IS_HASH, int NLOADS>
+ * registers. IS_HASH selects grouped aggregation. Single LDS buffer: the
+ * block stages one tile with stage_tile, barriers, and every lane parses its
+ * rows from LDS (d_row_collect, d_row_accumulate) before the next tile is
+ * staged. */
+template <int NAGGS, bool IS_HASH>
 __global__ void __launch_bounds__(THREADS, 2)
 k_scan_agg(ScanPlan plan,
            const uint8_t *__restrict__ vals, const uint64_t *__restrict__ val_offs,
@@ -1305,11 +1816,6 @@ k_scan_agg(ScanPlan plan,
   #pragma unroll
   for (int a = 0; a < NAGGS; a++) { l_cnt[a] = 0; l_lo[a] = 0; l_hi[a] = 0; }
 
-  int needed = (plan.has_filter ? 1 : 0) + (plan.filter2_on ? 1 : 0) + (IS_HASH ? 1 : 0);
-  #pragma unroll
-  for (int a = 0; a < NAGGS; a++)
-    if (plan.aggs[a].kind != DAGG_COUNT_ROWS) needed++;
-
   bool any_parse_err = false;
 
   /* per-block LDS pre-aggregation table (hash mode): keys + accumulators
@@ -1321,12 +1827,7 @@ k_scan_agg(ScanPlan plan,
   if (IS_HASH && LSLOTS) {
     lkeys = (long long *)(lds + plan.lds_agg_off);
     laccs = (SimpleAggAcc *)(lkeys + LSLOTS);
-    for (uint32_t s = threadIdx.x; s < LSLOTS; s += blockDim.x) {
-      lkeys[s] = (long long)0x8000000000000000ll;
-      #pragma unroll
-      for (int a = 0; a < NAGGS; a++)
-        laccs[s * NAGGS + a] = SimpleAggAcc{0, 0, 0};
-    }
+    d_hash_lds_init<NAGGS>(plan, lkeys, laccs, LSLOTS);
     __syncthreads();
   }
 
@@ -1345,433 +1846,26 @@ k_scan_agg(ScanPlan plan,
     for (uint64_t my_row = row0 + threadIdx.x; my_row < row1; my_row += blockDim.x) {
       const uint8_t *vp = lds + shift + (uint32_t)(val_offs[my_row] - gbase);
       uint32_t vlen = (uint32_t)(val_offs[my_row + 1] - val_offs[my_row]);
-      bool parse_ok = true;
-
-      bool filt_found = false, filt_null = false; int64_t filt_v = 0;
-      bool f2_found = false, f2_null = false; int64_t f2_v = 0;
-      bool grp_found = false, grp_null = false; int64_t grp_v = 0;
+      RowVals rv;
       AggColView cols[NAGGS];
-      #pragma unroll
-      for (int a = 0; a < NAGGS; a++) cols[a] = {false, false, false, 0, 0, 0, nullptr, 0};
-      int found = 0;
-
-      if (plan.index_mode) {
-        int64_t hval = 0; bool hfound = false;
-        parse_ok = d_index_collect<NAGGS, IS_HASH>(plan, vp, vlen, my_row,
-                                                   &filt_found, &filt_null,
-                                                   &filt_v, &grp_found,
-                                                   &grp_null, &grp_v, cols,
-                                                   &hval, &hfound);
-      } else if (!(vlen == 0 || (vlen == 1 && vp[0] == 0))) {
-        /* directory fast path: one direct next_cell per needed column
-           instead of a sequential walk over every cell */
-        bool dir_done = false;
-        if (plan.celldir && vp[0] != 128) {
-          const uint8_t *db = plan.celldir;
-          const uint64_t dn = plan.celldir_n;
-          uint32_t d_f = 0xFFu, d_f2 = 0xFFu, d_g = 0xFFu, d_a[NAGGS];
-          bool seq = false;
-          if (plan.has_filter)
-            d_f = db[(uint64_t)(plan.filter_col_id - 1) * dn + my_row];
-          if (plan.filter2_on)
-            d_f2 = db[(uint64_t)(plan.filter2_col_id - 1) * dn + my_row];
-          if (IS_HASH)
-            d_g = db[(uint64_t)(plan.group_col_id - 1) * dn + my_row];
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++) {
-            d_a[a] = 0xFFu;
-            if (plan.aggs[a].kind != DAGG_COUNT_ROWS)
-              d_a[a] = db[(uint64_t)(plan.aggs[a].col_id - 1) * dn + my_row];
-          }
-          seq = (d_f == 0xFEu) | (d_f2 == 0xFEu) | (d_g == 0xFEu);
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++) seq |= (d_a[a] == 0xFEu);
-          if (!seq) {
-            dir_done = true;
-            int64_t cid; uint32_t coff; CellView cell; uint32_t pos;
-            if (plan.has_filter && d_f != 0xFFu) {
-              pos = d_f;
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.filter_col_id) {
-                filt_found = true;
-                if (cell.is_null) filt_null = true;
-                else if (plan.filter_is_real ? cell.has_real : cell.has_int) filt_v = cell.ival;
-                else parse_ok = false;
-              } else parse_ok = false;
-            }
-            if (plan.filter2_on && d_f2 != 0xFFu) {
-              pos = d_f2;
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.filter2_col_id) {
-                f2_found = true;
-                if (cell.is_null) f2_null = true;
-                else if (plan.filter2_is_real ? cell.has_real : cell.has_int) f2_v = cell.ival;
-                else parse_ok = false;
-              } else parse_ok = false;
-            }
-            if (IS_HASH && d_g != 0xFFu) {
-              pos = d_g;
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.group_col_id) {
-                grp_found = true;
-                if (cell.is_null) grp_null = true;
-                else if (cell.has_int) grp_v = cell.ival;
-                else parse_ok = false;
-              } else parse_ok = false;
-            }
-            #pragma unroll
-            for (int a = 0; a < NAGGS; a++) {
-              if (plan.aggs[a].kind == DAGG_COUNT_ROWS || d_a[a] == 0xFFu)
-                continue;
-              if (IS_HASH && grp_found && !grp_null && parse_ok &&
-                  plan.aggs[a].col_id == plan.group_col_id &&
-                  plan.aggs[a].kind != DAGG_SUM_DEC &&
-                  plan.aggs[a].kind != DAGG_SUM_REAL) {
-                /* agg over the GROUP column: reuse the parsed int value
-                   (avg/sum BY the same column parses the cell once) */
-                cols[a].found = true;
-                cols[a].null = false;
-                cols[a].iv = grp_v;
-                continue;
-              }
-              if (IS_HASH && grp_found && grp_null && parse_ok &&
-                  plan.aggs[a].col_id == plan.group_col_id) {
-                cols[a].found = true;
-                cols[a].null = true;
-                continue;
-              }
-              pos = d_a[a];
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.aggs[a].col_id) {
-                cols[a].found = true;
-                cols[a].null = cell.is_null;
-                cols[a].iv = cell.ival;
-                cols[a].has_dec = cell.has_dec;
-                cols[a].dsc = cell.dscaled; cols[a].dfr = cell.dfrac;
-                cols[a].dwide = cell.dwide; cols[a].dwrem = cell.dwide_rem;
-                if (!cell.is_null && !cell.has_int && !cell.has_real &&
-                    !cell.has_dec && !cell.dwide)
-                  parse_ok = false;
-              } else parse_ok = false;
-            }
-          }
-        }
-        if (dir_done) {
-        } else if (vp[0] == 128) {   /* row v2 */
-        parse_ok = d_v2_collect<NAGGS, IS_HASH>(plan, vp, vlen,
-                                                &filt_found, &filt_null, &filt_v,
-                                                &grp_found, &grp_null, &grp_v,
-                                                cols, true,
-                                                &f2_found, &f2_null, &f2_v);
-        } else {
-        uint32_t pos = 0;
-        while (pos < vlen) {
-          int64_t cell_id;
-          uint32_t cell_off;
-          CellView cell;
-          if (!next_cell(vp, vlen, &pos, &cell_id, &cell_off, &cell)) {
-            parse_ok = false;
-            break;
-          }
-          if (plan.has_filter && !filt_found && cell_id == plan.filter_col_id) {
-            filt_found = true;
-            if (cell.is_null) filt_null = true;
-            else if (plan.filter_is_real ? cell.has_real : cell.has_int) filt_v = cell.ival;
-            else parse_ok = false;
-            found++;
-          }
-          if (plan.filter2_on && !f2_found && cell_id == plan.filter2_col_id) {
-            f2_found = true;
-            if (cell.is_null) f2_null = true;
-            else if (plan.filter2_is_real ? cell.has_real : cell.has_int) f2_v = cell.ival;
-            else parse_ok = false;
-            found++;
-          }
-          if (IS_HASH && !grp_found && cell_id == plan.group_col_id) {
-            grp_found = true;
-            if (cell.is_null) grp_null = true;
-            else if (cell.has_int) grp_v = cell.ival;
-            else parse_ok = false;
-            found++;
-          }
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++) {
-            if (plan.aggs[a].kind == DAGG_COUNT_ROWS || cols[a].found) continue;
-            if (cell_id == plan.aggs[a].col_id) {
-              cols[a].found = true;
-              cols[a].null = cell.is_null;
-              cols[a].iv = cell.ival;
-              cols[a].has_dec = cell.has_dec;
-              cols[a].dsc = cell.dscaled; cols[a].dfr = cell.dfrac;
-              cols[a].dwide = cell.dwide; cols[a].dwrem = cell.dwide_rem;
-              if (!cell.is_null && !cell.has_int && !cell.has_real && !cell.has_dec && !cell.dwide) parse_ok = false;
-              found++;
-            }
-          }
-          if (found >= needed) break;
-        }
-        }  /* v1/v2 */
-      }
-
-      int64_t xv0_ = 0, xv1_ = 0;
-      uint8_t xn0_ = 0, xn1_ = 0;
-      if (plan.n_xcap)
-        d_xcap_extract(plan, cols, &xv0_, &xn0_, &xv1_, &xn1_);
-      if (!parse_ok) {
-        any_parse_err = true;
-      } else if (bool ke = false;
-                 d_keep2(plan, filt_found, filt_null, filt_v, f2_found,
-                         f2_null, f2_v, &ke, xv0_, xn0_, xv1_, xn1_)
-                     ? true
-                     : (ke ? (any_parse_err = true, false) : false)) {
-        SimpleAggAcc *acc_base = nullptr;
-        unsigned long long *ext_base = nullptr;
-        /* conservative wide-decimal pre-pass: rows that may need a 256-bit
-           add must take a GLOBAL slot (the LDS table is 128-bit) */
-        bool row_wide = false;
-        if (IS_HASH) {
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++) {
-            if (plan.aggs[a].kind != DAGG_SUM_DEC || !cols[a].found ||
-                cols[a].null)
-              continue;
-            if (cols[a].dwide) { row_wide = true; continue; }
-            if (!cols[a].has_dec) continue;
-            int d = plan.aggs[a].target_frac - cols[a].dfr;
-            if (d > 18) { row_wide = true; continue; }
-            if (d > 0) {
-              int64_t lim = (int64_t)(0x7FFFFFFFFFFFFFFFll);
-              for (int t = 0; t < d; t++) lim /= 10;
-              if (cols[a].dsc > lim || cols[a].dsc < -lim) row_wide = true;
-            }
-          }
-        }
-        if (IS_HASH) {
-          if (!grp_found || grp_null) {
-            atomicAdd(&ht.rsvd_seen[1], 1ull);
-            acc_base = ht.reserved + 1 * NAGGS;
-            if (ht.rsvd_ext) ext_base = ht.rsvd_ext + 1 * NAGGS * 2;
-          } else if (grp_v == (long long)0x8000000000000000ll) {
-            atomicAdd(&ht.rsvd_seen[0], 1ull);
-            acc_base = ht.reserved + 0 * NAGGS;
-            if (ht.rsvd_ext) ext_base = ht.rsvd_ext + 0 * NAGGS * 2;
-          } else {
-            const unsigned long long EMPTY = 0x8000000000000000ull;
-            uint64_t h = (uint64_t)grp_v * 0x9E3779B97F4A7C15ull;
-            h ^= h >> 29;
-            bool in_lds = false;
-            if (LSLOTS && !row_wide) {
-              /* per-block LDS table first; fall through to global if full */
-              uint32_t lmask = LSLOTS - 1u;
-              uint32_t slot = (uint32_t)(h & lmask);
-              for (uint32_t probe = 0; probe <= lmask / 2; probe++) {
-                unsigned long long curk =
-                    atomicCAS((unsigned long long *)&lkeys[slot], EMPTY,
-                              (unsigned long long)grp_v);
-                if (curk == EMPTY || curk == (unsigned long long)grp_v) {
-                  acc_base = laccs + (uint64_t)slot * NAGGS;
-                  in_lds = true;
-                  break;
-                }
-                slot = (slot + 1) & lmask;
-              }
-            }
-            if (!in_lds) {
-              uint32_t mask = plan.table_size - 1u;
-              uint32_t slot = (uint32_t)(h & mask);
-              for (uint32_t probe = 0; ; probe++) {
-                if (probe > mask) { atomicOr(ht.error, 1u); break; }
-                unsigned long long curk =
-                    atomicCAS((unsigned long long *)&ht.keys[slot], EMPTY,
-                              (unsigned long long)grp_v);
-                if (curk == EMPTY) {
-                  atomicAdd(ht.n_groups, 1ull);
-                  acc_base = ht.accs + (uint64_t)slot * NAGGS;
-                  if (ht.ext) ext_base = ht.ext + (uint64_t)slot * NAGGS * 2;
-                  break;
-                }
-                if (curk == (unsigned long long)grp_v) {
-                  acc_base = ht.accs + (uint64_t)slot * NAGGS;
-                  if (ht.ext) ext_base = ht.ext + (uint64_t)slot * NAGGS * 2;
-                  break;
-                }
-                slot = (slot + 1) & mask;
-              }
-            }
-          }
-        }
-        #pragma unroll
-        for (int a = 0; a < NAGGS; a++) {
-          const DevAggSpec &sp = plan.aggs[a];
-          bool contribute;
-          bool dec_wide = false;       /* value does not fit a scaled i64 */
-          __int128 vw = 0;
-          int64_t v = 0;
-          if (sp.kind == DAGG_XCAP) {
-            continue;                    /* capture-only channel */
-          } else if (sp.kind == DAGG_COUNT_ROWS) {
-            contribute = true;
-          } else if (!cols[a].found || cols[a].null) {
-            contribute = false;
-          } else if (sp.kind == DAGG_COUNT_COL) {
-            contribute = true;
-          } else if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_REAL ||
-                     d_is_fold(sp.kind)) {
-            contribute = true; v = cols[a].iv;
-          } else {  /* SUM_DEC: values to 38 digits via the i128 parse;
-                         a scaled value past i64 goes to the 256-bit path */
-            __int128 sv = 0;
-            int32_t fr = 0;
-            bool okd = true;
-            if (cols[a].has_dec) {
-              sv = cols[a].dsc;
-              fr = cols[a].dfr;
-            } else if (cols[a].dwide) {
-              if (!d_decimal_scaled128(cols[a].dwide, cols[a].dwrem, &sv, &fr))
-                okd = false;
-            } else {
-              okd = false;
-            }
-            int d = okd ? sp.target_frac - fr : -1;
-            if (!okd || d < 0 || d > 38) {
-              any_parse_err = true;
-              contribute = false;
-            } else {
-              const __int128 LIM =
-                  (__int128)(((unsigned __int128)~(unsigned __int128)0) >> 1) / 10;
-              bool ovf = false;
-              for (int t = 0; t < d; t++) {
-                if (sv > LIM || sv < -LIM) { ovf = true; break; }
-                sv *= 10;
-              }
-              if (ovf) {
-                any_parse_err = true;       /* > 38-digit scaled: loud */
-                contribute = false;
-              } else if (sv >= (__int128)INT64_MIN && sv <= (__int128)INT64_MAX) {
-                v = (int64_t)sv;
-                contribute = true;
-              } else {
-                vw = sv;
-                dec_wide = true;
-                contribute = true;
-              }
-            }
-          }
-          if (!contribute) continue;
-          if (IS_HASH) {
-            if (acc_base) {
-              atomicAdd(&acc_base[a].cnt, 1ull);
-              if (sp.kind == DAGG_SUM_REAL)
-                atomicAdd((double *)&acc_base[a].sum_lo,
-                          __longlong_as_double(v));
-              else if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_DEC) {
-                /* a 256-bit acc must see EVERY add as i256 — a narrow
-                   negative i128 add would not borrow from the ext limbs */
-                if (ext_base) {
-                  atomic_add_i256(&acc_base[a].sum_lo, &acc_base[a].sum_hi,
-                                  ext_base + a * 2,
-                                  dec_wide ? vw : (__int128)v);
-                } else if (dec_wide) {
-                  any_parse_err = true;     /* no ext buffers: loud */
-                } else {
-                  atomic_add_i128(&acc_base[a].sum_lo, &acc_base[a].sum_hi, v);
-                }
-              }
-              else if (d_is_fold(sp.kind)) {
-                unsigned long long b = d_fold_xform(sp.kind, v, sp.col_unsigned);
-                if (d_is_xor(sp.kind)) atomicXor(&acc_base[a].sum_lo, b);
-                else if (sp.kind == DAGG_MAX_INT || sp.kind == DAGG_MIN_INT || sp.kind == DAGG_MAX_REAL || sp.kind == DAGG_MIN_REAL)
-                  atomicMax(&acc_base[a].sum_lo, b);
-                else atomicOr(&acc_base[a].sum_lo, b);
-              }
-            }
-          } else {
-            l_cnt[a]++;
-            if (sp.kind == DAGG_SUM_REAL) {
-              l_lo[a] = (unsigned long long)__double_as_longlong(
-                  __longlong_as_double((long long)l_lo[a]) +
-                  __longlong_as_double(v));
-            } else if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_DEC) {
-              if (dec_wide) {
-                /* wide values go straight to the 256-bit global acc; the
-                   per-lane i128 partial keeps only i64-fitting values */
-                if (plan.simple_ext)
-                  atomic_add_i256(&simple_acc[a].sum_lo, &simple_acc[a].sum_hi,
-                                  plan.simple_ext + a * 2, vw);
-                else
-                  any_parse_err = true;
-              } else {
-                unsigned long long old = l_lo[a];
-                unsigned long long nv = old + (unsigned long long)v;
-                l_hi[a] += (nv < old ? 1 : 0) + (v < 0 ? -1 : 0);
-                l_lo[a] = nv;
-              }
-            } else if (d_is_fold(sp.kind)) {
-              unsigned long long b = d_fold_xform(sp.kind, v, sp.col_unsigned);
-              if (d_is_xor(sp.kind)) l_lo[a] ^= b;
-              else if (sp.kind == DAGG_MAX_INT || sp.kind == DAGG_MIN_INT || sp.kind == DAGG_MAX_REAL || sp.kind == DAGG_MIN_REAL)
-                l_lo[a] = l_lo[a] > b ? l_lo[a] : b;
-              else l_lo[a] |= b;
-            }
-          }
-        }
-      }
+      const uint8_t *db = plan.celldir;
+      const uint64_t dn = plan.celldir_n;
+      bool parse_ok = d_row_collect<NAGGS, IS_HASH, false>(
+          plan, vp, vlen, my_row,
+          [&](int32_t, int64_t cid) -> uint32_t {
+            return (uint32_t)db[(uint64_t)(cid - 1) * dn + my_row];
+          },
+          rv, cols);
+      any_parse_err |= d_row_accumulate<NAGGS, IS_HASH>(
+          plan, parse_ok, rv, cols, ht, lkeys, laccs, LSLOTS, simple_acc, l_cnt,
+          l_lo, l_hi);
     }
   }
 
   /* flush the block's LDS pre-agg table into the global table */
   if (IS_HASH && LSLOTS) {
     __syncthreads();
-    const unsigned long long EMPTY = 0x8000000000000000ull;
-    uint32_t mask = plan.table_size - 1u;
-    for (uint32_t s = threadIdx.x; s < LSLOTS; s += blockDim.x) {
-      long long key = lkeys[s];
-      if (key == (long long)0x8000000000000000ll) continue;
-      uint64_t h = (uint64_t)key * 0x9E3779B97F4A7C15ull;
-      h ^= h >> 29;
-      uint32_t slot = (uint32_t)(h & mask);
-      SimpleAggAcc *gacc = nullptr;
-      unsigned long long *gext = nullptr;
-      for (uint32_t probe = 0; ; probe++) {
-        if (probe > mask) { atomicOr(ht.error, 1u); break; }
-        unsigned long long curk =
-            atomicCAS((unsigned long long *)&ht.keys[slot], EMPTY,
-                      (unsigned long long)key);
-        if (curk == EMPTY) { atomicAdd(ht.n_groups, 1ull); gacc = ht.accs + (uint64_t)slot * NAGGS; break; }
-        if (curk == (unsigned long long)key) { gacc = ht.accs + (uint64_t)slot * NAGGS; break; }
-        slot = (slot + 1) & mask;
-      }
-      if (!gacc) continue;
-      if (ht.ext) gext = ht.ext + (uint64_t)slot * NAGGS * 2;
-      #pragma unroll
-      for (int a = 0; a < NAGGS; a++) {
-        const SimpleAggAcc &la = laccs[s * NAGGS + a];
-        const int32_t kind = plan.aggs[a].kind;
-        if (la.cnt) atomicAdd(&gacc[a].cnt, la.cnt);
-        if (d_is_fold(kind)) {
-          if (la.sum_lo) {
-            if (d_is_xor(kind)) atomicXor(&gacc[a].sum_lo, la.sum_lo);
-            else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT || kind == DAGG_MAX_REAL || kind == DAGG_MIN_REAL)
-              atomicMax(&gacc[a].sum_lo, la.sum_lo);
-            else atomicOr(&gacc[a].sum_lo, la.sum_lo);
-          }
-          continue;
-        }
-        if (la.sum_lo | la.sum_hi) {
-          __int128 part = (__int128)(
-              ((unsigned __int128)la.sum_hi << 64) | la.sum_lo);
-          if (gext)
-            atomic_add_i256(&gacc[a].sum_lo, &gacc[a].sum_hi, gext + a * 2,
-                            part);
-          else {
-            unsigned long long old = atomicAdd(&gacc[a].sum_lo, la.sum_lo);
-            long long carry = (old + la.sum_lo < old) ? 1 : 0;
-            long long hi_add = (long long)la.sum_hi + carry;
-            if (hi_add) atomicAdd(&gacc[a].sum_hi, (unsigned long long)hi_add);
-          }
-        }
-      }
-    }
+    d_hash_lds_flush<NAGGS, false>(plan, ht, lkeys, laccs, LSLOTS);
   }
 
   if (!IS_HASH) d_simple_epilogue<NAGGS>(plan, simple_acc, l_cnt, l_lo, l_hi);
@@ -1810,11 +1904,6 @@ k_scan_agg_pipe(ScanPlan plan,
   #pragma unroll
   for (int a = 0; a < NAGGS; a++) { l_cnt[a] = 0; l_lo[a] = 0; l_hi[a] = 0; }
 
-  int needed = (plan.has_filter ? 1 : 0) + (plan.filter2_on ? 1 : 0) + (IS_HASH ? 1 : 0);
-  #pragma unroll
-  for (int a = 0; a < NAGGS; a++)
-    if (plan.aggs[a].kind != DAGG_COUNT_ROWS) needed++;
-
   bool any_parse_err = false;
 
   /* per-block LDS pre-aggregation table (hash mode, after the two DMA
@@ -1826,12 +1915,7 @@ k_scan_agg_pipe(ScanPlan plan,
   if (IS_HASH && LSLOTS) {
     lkeys = (long long *)(lds + plan.lds_agg_off);
     laccs = (SimpleAggAcc *)(lkeys + LSLOTS);
-    for (uint32_t s = threadIdx.x; s < LSLOTS; s += blockDim.x) {
-      lkeys[s] = (long long)0x8000000000000000ll;
-      #pragma unroll
-      for (int a = 0; a < NAGGS; a++)
-        laccs[s * NAGGS + a] = SimpleAggAcc{0, 0, 0};
-    }
+    d_hash_lds_init<NAGGS>(plan, lkeys, laccs, LSLOTS);
     __syncthreads();
   }
 
@@ -2040,384 +2124,25 @@ k_scan_agg_pipe(ScanPlan plan,
       uint64_t o0 = loffs[r], o1 = loffs[r + 1];
       const uint8_t *vp = bv + shift + (uint32_t)(o0 - gb);
       uint32_t vlen = (uint32_t)(o1 - o0);
-      bool parse_ok = true;
-
-      bool filt_found = false, filt_null = false; int64_t filt_v = 0;
-      bool f2_found = false, f2_null = false; int64_t f2_v = 0;
-      bool grp_found = false, grp_null = false; int64_t grp_v = 0;
+      RowVals rv;
       AggColView cols[NAGGS];
-      #pragma unroll
-      for (int a = 0; a < NAGGS; a++) cols[a] = {false, false, false, 0, 0, 0, nullptr, 0};
-      int found = 0;
-
-      if (plan.index_mode) {
-        int64_t hval = 0; bool hfound = false;
-        parse_ok = d_index_collect<NAGGS, IS_HASH>(plan, vp, vlen, my_row,
-                                                   &filt_found, &filt_null,
-                                                   &filt_v, &grp_found,
-                                                   &grp_null, &grp_v, cols,
-                                                   &hval, &hfound);
-      } else if (!(vlen == 0 || (vlen == 1 && vp[0] == 0))) {
-        /* directory fast path: one direct next_cell per needed column
-           instead of a sequential walk over every cell */
-        bool dir_done = false;
-        if (plan.celldir && vp[0] != 128) {
-          const uint8_t *db = plan.celldir;
-          const uint64_t dn = plan.celldir_n;
-          /* dir bytes come from the DMA-staged tile slices when assigned
-             (they head the parse dependency chain; a per-row random global
-             load here parks the wave ~L2/HBM latency per row) */
-          const uint8_t *b_dirs = b + DOFF;
-          auto dload = [&](int32_t slab, int64_t cid) -> uint32_t {
+      const uint8_t *db = plan.celldir;
+      const uint64_t dn = plan.celldir_n;
+      /* dir bytes come from the DMA-staged tile slices when assigned
+         (they head the parse dependency chain; a per-row random global
+         load here parks the wave ~L2/HBM latency per row) */
+      const uint8_t *b_dirs = b + DOFF;
+      bool parse_ok = d_row_collect<NAGGS, IS_HASH, false>(
+          plan, vp, vlen, my_row,
+          [&](int32_t slab, int64_t cid) -> uint32_t {
             return (DS && slab >= 0)
                        ? (uint32_t)b_dirs[(uint32_t)slab * 1024u + r]
                        : (uint32_t)db[(uint64_t)(cid - 1) * dn + my_row];
-          };
-          uint32_t d_f = 0xFFu, d_f2 = 0xFFu, d_g = 0xFFu, d_a[NAGGS];
-          bool seq = false;
-          if (plan.has_filter) d_f = dload(plan.dirslab_f, plan.filter_col_id);
-          if (plan.filter2_on)
-            d_f2 = dload(plan.dirslab_f2, plan.filter2_col_id);
-          if (IS_HASH) d_g = dload(plan.dirslab_g, plan.group_col_id);
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++) {
-            d_a[a] = 0xFFu;
-            if (plan.aggs[a].kind != DAGG_COUNT_ROWS)
-              d_a[a] = dload(plan.dirslab_a[a], plan.aggs[a].col_id);
-          }
-          seq = (d_f == 0xFEu) | (d_f2 == 0xFEu) | (d_g == 0xFEu);
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++) seq |= (d_a[a] == 0xFEu);
-          if (!seq) {
-            dir_done = true;
-            int64_t cid; uint32_t coff; CellView cell; uint32_t pos;
-            if (plan.has_filter && d_f != 0xFFu) {
-              pos = d_f;
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.filter_col_id) {
-                filt_found = true;
-                if (cell.is_null) filt_null = true;
-                else if (plan.filter_is_real ? cell.has_real : cell.has_int) filt_v = cell.ival;
-                else parse_ok = false;
-              } else parse_ok = false;
-            }
-            if (plan.filter2_on && d_f2 != 0xFFu) {
-              pos = d_f2;
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.filter2_col_id) {
-                f2_found = true;
-                if (cell.is_null) f2_null = true;
-                else if (plan.filter2_is_real ? cell.has_real : cell.has_int) f2_v = cell.ival;
-                else parse_ok = false;
-              } else parse_ok = false;
-            }
-            if (IS_HASH && d_g != 0xFFu) {
-              pos = d_g;
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.group_col_id) {
-                grp_found = true;
-                if (cell.is_null) grp_null = true;
-                else if (cell.has_int) grp_v = cell.ival;
-                else parse_ok = false;
-              } else parse_ok = false;
-            }
-            #pragma unroll
-            for (int a = 0; a < NAGGS; a++) {
-              if (plan.aggs[a].kind == DAGG_COUNT_ROWS || d_a[a] == 0xFFu)
-                continue;
-              if (IS_HASH && grp_found && !grp_null && parse_ok &&
-                  plan.aggs[a].col_id == plan.group_col_id &&
-                  plan.aggs[a].kind != DAGG_SUM_DEC &&
-                  plan.aggs[a].kind != DAGG_SUM_REAL) {
-                /* agg over the GROUP column: reuse the parsed int value
-                   (avg/sum BY the same column parses the cell once) */
-                cols[a].found = true;
-                cols[a].null = false;
-                cols[a].iv = grp_v;
-                continue;
-              }
-              if (IS_HASH && grp_found && grp_null && parse_ok &&
-                  plan.aggs[a].col_id == plan.group_col_id) {
-                cols[a].found = true;
-                cols[a].null = true;
-                continue;
-              }
-              pos = d_a[a];
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.aggs[a].col_id) {
-                cols[a].found = true;
-                cols[a].null = cell.is_null;
-                cols[a].iv = cell.ival;
-                cols[a].has_dec = cell.has_dec;
-                cols[a].dsc = cell.dscaled; cols[a].dfr = cell.dfrac;
-                cols[a].dwide = cell.dwide; cols[a].dwrem = cell.dwide_rem;
-                if (!cell.is_null && !cell.has_int && !cell.has_real &&
-                    !cell.has_dec && !cell.dwide)
-                  parse_ok = false;
-              } else parse_ok = false;
-            }
-          }
-        }
-        if (dir_done) {
-        } else if (vp[0] == 128) {   /* row v2 */
-        parse_ok = d_v2_collect<NAGGS, IS_HASH>(plan, vp, vlen,
-                                                &filt_found, &filt_null, &filt_v,
-                                                &grp_found, &grp_null, &grp_v,
-                                                cols, true,
-                                                &f2_found, &f2_null, &f2_v);
-        } else {
-        uint32_t pos = 0;
-        while (pos < vlen) {
-          int64_t cell_id;
-          uint32_t cell_off;
-          CellView cell;
-          if (!next_cell(vp, vlen, &pos, &cell_id, &cell_off, &cell)) {
-            parse_ok = false;
-            break;
-          }
-          if (plan.has_filter && !filt_found && cell_id == plan.filter_col_id) {
-            filt_found = true;
-            if (cell.is_null) filt_null = true;
-            else if (plan.filter_is_real ? cell.has_real : cell.has_int) filt_v = cell.ival;
-            else parse_ok = false;
-            found++;
-          }
-          if (plan.filter2_on && !f2_found && cell_id == plan.filter2_col_id) {
-            f2_found = true;
-            if (cell.is_null) f2_null = true;
-            else if (plan.filter2_is_real ? cell.has_real : cell.has_int) f2_v = cell.ival;
-            else parse_ok = false;
-            found++;
-          }
-          if (IS_HASH && !grp_found && cell_id == plan.group_col_id) {
-            grp_found = true;
-            if (cell.is_null) grp_null = true;
-            else if (cell.has_int) grp_v = cell.ival;
-            else parse_ok = false;
-            found++;
-          }
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++) {
-            if (plan.aggs[a].kind == DAGG_COUNT_ROWS || cols[a].found) continue;
-            if (cell_id == plan.aggs[a].col_id) {
-              cols[a].found = true;
-              cols[a].null = cell.is_null;
-              cols[a].iv = cell.ival;
-              cols[a].has_dec = cell.has_dec;
-              cols[a].dsc = cell.dscaled; cols[a].dfr = cell.dfrac;
-              cols[a].dwide = cell.dwide; cols[a].dwrem = cell.dwide_rem;
-              if (!cell.is_null && !cell.has_int && !cell.has_real && !cell.has_dec && !cell.dwide) parse_ok = false;
-              found++;
-            }
-          }
-          if (found >= needed) break;
-        }
-        }  /* v1/v2 */
-      }
-
-      int64_t xv0_ = 0, xv1_ = 0;
-      uint8_t xn0_ = 0, xn1_ = 0;
-      if (plan.n_xcap)
-        d_xcap_extract(plan, cols, &xv0_, &xn0_, &xv1_, &xn1_);
-      if (!parse_ok) {
-        any_parse_err = true;
-      } else if (bool ke = false;
-                 d_keep2(plan, filt_found, filt_null, filt_v, f2_found,
-                         f2_null, f2_v, &ke, xv0_, xn0_, xv1_, xn1_)
-                     ? true
-                     : (ke ? (any_parse_err = true, false) : false)) {
-        SimpleAggAcc *acc_base = nullptr;
-        unsigned long long *ext_base = nullptr;
-        /* conservative wide-decimal pre-pass: rows that may need a 256-bit
-           add must take a GLOBAL slot (the LDS table is 128-bit) */
-        bool row_wide = false;
-        if (IS_HASH) {
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++) {
-            if (plan.aggs[a].kind != DAGG_SUM_DEC || !cols[a].found ||
-                cols[a].null)
-              continue;
-            if (cols[a].dwide) { row_wide = true; continue; }
-            if (!cols[a].has_dec) continue;
-            int d = plan.aggs[a].target_frac - cols[a].dfr;
-            if (d > 18) { row_wide = true; continue; }
-            if (d > 0) {
-              int64_t lim = (int64_t)(0x7FFFFFFFFFFFFFFFll);
-              for (int t = 0; t < d; t++) lim /= 10;
-              if (cols[a].dsc > lim || cols[a].dsc < -lim) row_wide = true;
-            }
-          }
-        }
-        if (IS_HASH) {
-          if (!grp_found || grp_null) {
-            atomicAdd(&ht.rsvd_seen[1], 1ull);
-            acc_base = ht.reserved + 1 * NAGGS;
-            if (ht.rsvd_ext) ext_base = ht.rsvd_ext + 1 * NAGGS * 2;
-          } else if (grp_v == (long long)0x8000000000000000ll) {
-            atomicAdd(&ht.rsvd_seen[0], 1ull);
-            acc_base = ht.reserved + 0 * NAGGS;
-            if (ht.rsvd_ext) ext_base = ht.rsvd_ext + 0 * NAGGS * 2;
-          } else {
-            uint64_t h = (uint64_t)grp_v * 0x9E3779B97F4A7C15ull;
-            h ^= h >> 29;
-            const unsigned long long EMPTY = 0x8000000000000000ull;
-            bool in_lds = false;
-            if (LSLOTS && !row_wide) {
-              /* per-block LDS table first; fall through to global if full */
-              uint32_t lmask = LSLOTS - 1u;
-              uint32_t slot = (uint32_t)(h & lmask);
-              for (uint32_t probe = 0; probe <= lmask / 2; probe++) {
-                unsigned long long curk =
-                    atomicCAS((unsigned long long *)&lkeys[slot], EMPTY,
-                              (unsigned long long)grp_v);
-                if (curk == EMPTY || curk == (unsigned long long)grp_v) {
-                  acc_base = laccs + (uint64_t)slot * NAGGS;
-                  in_lds = true;
-                  break;
-                }
-                slot = (slot + 1) & lmask;
-              }
-            }
-            if (!in_lds) {
-              uint32_t mask = plan.table_size - 1u;
-              uint32_t slot = (uint32_t)(h & mask);
-              for (uint32_t probe = 0; ; probe++) {
-                if (probe > mask) { atomicOr(ht.error, 1u); break; }
-                unsigned long long curk =
-                    atomicCAS((unsigned long long *)&ht.keys[slot], EMPTY,
-                              (unsigned long long)grp_v);
-                if (curk == EMPTY) {
-                  atomicAdd(ht.n_groups, 1ull);
-                  acc_base = ht.accs + (uint64_t)slot * NAGGS;
-                  if (ht.ext) ext_base = ht.ext + (uint64_t)slot * NAGGS * 2;
-                  break;
-                }
-                if (curk == (unsigned long long)grp_v) {
-                  acc_base = ht.accs + (uint64_t)slot * NAGGS;
-                  if (ht.ext) ext_base = ht.ext + (uint64_t)slot * NAGGS * 2;
-                  break;
-                }
-                slot = (slot + 1) & mask;
-              }
-            }
-          }
-        }
-        #pragma unroll
-        for (int a = 0; a < NAGGS; a++) {
-          const DevAggSpec &sp = plan.aggs[a];
-          bool contribute;
-          bool dec_wide = false;       /* value does not fit a scaled i64 */
-          __int128 vw = 0;
-          int64_t v = 0;
-          if (sp.kind == DAGG_XCAP) {
-            continue;                    /* capture-only channel */
-          } else if (sp.kind == DAGG_COUNT_ROWS) {
-            contribute = true;
-          } else if (!cols[a].found || cols[a].null) {
-            contribute = false;
-          } else if (sp.kind == DAGG_COUNT_COL) {
-            contribute = true;
-          } else if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_REAL ||
-                     d_is_fold(sp.kind)) {
-            contribute = true; v = cols[a].iv;
-          } else {  /* SUM_DEC: values to 38 digits via the i128 parse;
-                         a scaled value past i64 goes to the 256-bit path */
-            __int128 sv = 0;
-            int32_t fr = 0;
-            bool okd = true;
-            if (cols[a].has_dec) {
-              sv = cols[a].dsc;
-              fr = cols[a].dfr;
-            } else if (cols[a].dwide) {
-              if (!d_decimal_scaled128(cols[a].dwide, cols[a].dwrem, &sv, &fr))
-                okd = false;
-            } else {
-              okd = false;
-            }
-            int d = okd ? sp.target_frac - fr : -1;
-            if (!okd || d < 0 || d > 38) {
-              any_parse_err = true;
-              contribute = false;
-            } else {
-              const __int128 LIM =
-                  (__int128)(((unsigned __int128)~(unsigned __int128)0) >> 1) / 10;
-              bool ovf = false;
-              for (int t = 0; t < d; t++) {
-                if (sv > LIM || sv < -LIM) { ovf = true; break; }
-                sv *= 10;
-              }
-              if (ovf) {
-                any_parse_err = true;       /* > 38-digit scaled: loud */
-                contribute = false;
-              } else if (sv >= (__int128)INT64_MIN && sv <= (__int128)INT64_MAX) {
-                v = (int64_t)sv;
-                contribute = true;
-              } else {
-                vw = sv;
-                dec_wide = true;
-                contribute = true;
-              }
-            }
-          }
-          if (!contribute) continue;
-          if (IS_HASH) {
-            if (acc_base) {
-              atomicAdd(&acc_base[a].cnt, 1ull);
-              if (sp.kind == DAGG_SUM_REAL)
-                atomicAdd((double *)&acc_base[a].sum_lo,
-                          __longlong_as_double(v));
-              else if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_DEC) {
-                /* a 256-bit acc must see EVERY add as i256 — a narrow
-                   negative i128 add would not borrow from the ext limbs */
-                if (ext_base) {
-                  atomic_add_i256(&acc_base[a].sum_lo, &acc_base[a].sum_hi,
-                                  ext_base + a * 2,
-                                  dec_wide ? vw : (__int128)v);
-                } else if (dec_wide) {
-                  any_parse_err = true;     /* no ext buffers: loud */
-                } else {
-                  atomic_add_i128(&acc_base[a].sum_lo, &acc_base[a].sum_hi, v);
-                }
-              }
-              else if (d_is_fold(sp.kind)) {
-                unsigned long long b = d_fold_xform(sp.kind, v, sp.col_unsigned);
-                if (d_is_xor(sp.kind)) atomicXor(&acc_base[a].sum_lo, b);
-                else if (sp.kind == DAGG_MAX_INT || sp.kind == DAGG_MIN_INT || sp.kind == DAGG_MAX_REAL || sp.kind == DAGG_MIN_REAL)
-                  atomicMax(&acc_base[a].sum_lo, b);
-                else atomicOr(&acc_base[a].sum_lo, b);
-              }
-            }
-          } else {
-            l_cnt[a]++;
-            if (sp.kind == DAGG_SUM_REAL) {
-              l_lo[a] = (unsigned long long)__double_as_longlong(
-                  __longlong_as_double((long long)l_lo[a]) +
-                  __longlong_as_double(v));
-            } else if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_DEC) {
-              if (dec_wide) {
-                /* wide values go straight to the 256-bit global acc; the
-                   per-lane i128 partial keeps only i64-fitting values */
-                if (plan.simple_ext)
-                  atomic_add_i256(&simple_acc[a].sum_lo, &simple_acc[a].sum_hi,
-                                  plan.simple_ext + a * 2, vw);
-                else
-                  any_parse_err = true;
-              } else {
-                unsigned long long old = l_lo[a];
-                unsigned long long nv = old + (unsigned long long)v;
-                l_hi[a] += (nv < old ? 1 : 0) + (v < 0 ? -1 : 0);
-                l_lo[a] = nv;
-              }
-            } else if (d_is_fold(sp.kind)) {
-              unsigned long long b = d_fold_xform(sp.kind, v, sp.col_unsigned);
-              if (d_is_xor(sp.kind)) l_lo[a] ^= b;
-              else if (sp.kind == DAGG_MAX_INT || sp.kind == DAGG_MIN_INT || sp.kind == DAGG_MAX_REAL || sp.kind == DAGG_MIN_REAL)
-                l_lo[a] = l_lo[a] > b ? l_lo[a] : b;
-              else l_lo[a] |= b;
-            }
-          }
-        }
-      }
+          },
+          rv, cols);
+      any_parse_err |= d_row_accumulate<NAGGS, IS_HASH>(
+          plan, parse_ok, rv, cols, ht, lkeys, laccs, LSLOTS, simple_acc, l_cnt,
+          l_lo, l_hi);
     }
     }  /* FASTFC else */
     }  /* !diag */
@@ -2427,56 +2152,7 @@ k_scan_agg_pipe(ScanPlan plan,
   /* flush the block's LDS pre-agg table into the global table */
   if (IS_HASH && LSLOTS) {
     __syncthreads();
-    const unsigned long long EMPTY = 0x8000000000000000ull;
-    uint32_t mask = plan.table_size - 1u;
-    for (uint32_t s = threadIdx.x; s < LSLOTS; s += blockDim.x) {
-      long long key = lkeys[s];
-      if (key == (long long)0x8000000000000000ll) continue;
-      uint64_t h = (uint64_t)key * 0x9E3779B97F4A7C15ull;
-      h ^= h >> 29;
-      uint32_t slot = (uint32_t)(h & mask);
-      SimpleAggAcc *gacc = nullptr;
-      unsigned long long *gext = nullptr;
-      for (uint32_t probe = 0; ; probe++) {
-        if (probe > mask) { atomicOr(ht.error, 1u); break; }
-        unsigned long long curk =
-            atomicCAS((unsigned long long *)&ht.keys[slot], EMPTY,
-                      (unsigned long long)key);
-        if (curk == EMPTY) { atomicAdd(ht.n_groups, 1ull); gacc = ht.accs + (uint64_t)slot * NAGGS; break; }
-        if (curk == (unsigned long long)key) { gacc = ht.accs + (uint64_t)slot * NAGGS; break; }
-        slot = (slot + 1) & mask;
-      }
-      if (!gacc) continue;
-      if (ht.ext) gext = ht.ext + (uint64_t)slot * NAGGS * 2;
-      #pragma unroll
-      for (int a = 0; a < NAGGS; a++) {
-        const SimpleAggAcc &la = laccs[s * NAGGS + a];
-        const int32_t kind = plan.aggs[a].kind;
-        if (la.cnt) atomicAdd(&gacc[a].cnt, la.cnt);
-        if (d_is_fold(kind)) {
-          if (la.sum_lo) {
-            if (d_is_xor(kind)) atomicXor(&gacc[a].sum_lo, la.sum_lo);
-            else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT || kind == DAGG_MAX_REAL || kind == DAGG_MIN_REAL)
-              atomicMax(&gacc[a].sum_lo, la.sum_lo);
-            else atomicOr(&gacc[a].sum_lo, la.sum_lo);
-          }
-          continue;
-        }
-        if (la.sum_lo | la.sum_hi) {
-          __int128 part = (__int128)(
-              ((unsigned __int128)la.sum_hi << 64) | la.sum_lo);
-          if (gext)
-            atomic_add_i256(&gacc[a].sum_lo, &gacc[a].sum_hi, gext + a * 2,
-                            part);
-          else {
-            unsigned long long old = atomicAdd(&gacc[a].sum_lo, la.sum_lo);
-            long long carry = (old + la.sum_lo < old) ? 1 : 0;
-            long long hi_add = (long long)la.sum_hi + carry;
-            if (hi_add) atomicAdd(&gacc[a].sum_hi, (unsigned long long)hi_add);
-          }
-        }
-      }
-    }
+    d_hash_lds_flush<NAGGS, false>(plan, ht, lkeys, laccs, LSLOTS);
   }
 
   if (!IS_HASH) d_simple_epilogue<NAGGS>(plan, simple_acc, l_cnt, l_lo, l_hi);
@@ -3243,149 +2919,7 @@ int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
   return (int)hipGetLastError();
 }
 
-/* ---------------- hash aggregation over column planes --------
- * The group-slot selection, the per-aggregate update and the LDS-table flush
- * below restate what the hash instantiations of k_scan_agg / k_scan_agg_pipe
- * do inline, so that a group lands in the same slot with the same
- * accumulator bits whichever kernel saw the row. */
-
-struct HashSlot { SimpleAggAcc *acc; unsigned long long *ext; };
-
-__device__ static inline uint64_t d_group_hash(int64_t key) {
-  uint64_t h = (uint64_t)key * 0x9E3779B97F4A7C15ull;
-  return h ^ (h >> 29);
-}
-
-/* find-or-claim key's slot in the global open-addressed table; a full table
-   raises ht.error[0] and returns a null acc (the host grows and retries).
-   na = the plan's n_aggs: the accumulator arrays are laid out with that
-   stride, whatever NAGGS the kernel instance unrolls to. */
-__device__ static inline HashSlot d_hash_global_slot(const HashAggTable &ht,
-                                                     uint32_t table_size,
-                                                     uint32_t na,
-                                                     int64_t key) {
-  const unsigned long long EMPTY = 0x8000000000000000ull;
-  HashSlot hs{nullptr, nullptr};
-  uint32_t mask = table_size - 1u;
-  uint32_t slot = (uint32_t)(d_group_hash(key) & mask);
-  for (uint32_t probe = 0; ; probe++) {
-    if (probe > mask) { atomicOr(ht.error, 1u); break; }
-    unsigned long long curk =
-        atomicCAS((unsigned long long *)&ht.keys[slot], EMPTY,
-                  (unsigned long long)key);
-    if (curk == EMPTY) atomicAdd(ht.n_groups, 1ull);
-    if (curk == EMPTY || curk == (unsigned long long)key) {
-      hs.acc = ht.accs + (uint64_t)slot * na;
-      if (ht.ext) hs.ext = ht.ext + (uint64_t)slot * na * 2;
-      break;
-    }
-    slot = (slot + 1) & mask;
-  }
-  return hs;
-}
-
-/* one kept row's accumulator block: NULL/absent keys -> reserved[1],
-   INT64_MIN (the EMPTY sentinel) -> reserved[0], everything else the block's
-   LDS pre-aggregation table first (128-bit accumulators, so never for a row
-   that may need a 256-bit add) and the global table when that is full */
-__device__ static inline HashSlot d_hash_row_slot(
-    const HashAggTable &ht, uint32_t table_size, uint32_t na, bool grp_found,
-    bool grp_null, int64_t grp_v, bool row_wide, long long *lkeys,
-    SimpleAggAcc *laccs, uint32_t lslots) {
-  HashSlot hs{nullptr, nullptr};
-  if (!grp_found || grp_null) {
-    atomicAdd(&ht.rsvd_seen[1], 1ull);
-    hs.acc = ht.reserved + 1 * na;
-    if (ht.rsvd_ext) hs.ext = ht.rsvd_ext + 1 * na * 2;
-    return hs;
-  }
-  if (grp_v == (long long)0x8000000000000000ll) {
-    atomicAdd(&ht.rsvd_seen[0], 1ull);
-    hs.acc = ht.reserved;
-    if (ht.rsvd_ext) hs.ext = ht.rsvd_ext;
-    return hs;
-  }
-  if (lslots && !row_wide) {
-    const unsigned long long EMPTY = 0x8000000000000000ull;
-    uint32_t lmask = lslots - 1u;
-    uint32_t slot = (uint32_t)(d_group_hash(grp_v) & lmask);
-    for (uint32_t probe = 0; probe <= lmask / 2; probe++) {
-      unsigned long long curk =
-          atomicCAS((unsigned long long *)&lkeys[slot], EMPTY,
-                    (unsigned long long)grp_v);
-      if (curk == EMPTY || curk == (unsigned long long)grp_v) {
-        hs.acc = laccs + (uint64_t)slot * na;
-        return hs;
-      }
-      slot = (slot + 1) & lmask;
-    }
-  }
-  return d_hash_global_slot(ht, table_size, na, grp_v);
-}
-
-/* one aggregate's contribution to its accumulator (LDS or global; ext = the
-   two high limbs when the accumulator is 256-bit). A 256-bit accumulator
-   must see every add as i256: a narrow negative i128 add would not borrow
-   from the ext limbs. False = a wide value met a 128-bit accumulator. */
-__device__ static inline bool d_hash_update(const DevAggSpec &sp,
-                                            SimpleAggAcc *acc,
-                                            unsigned long long *ext,
-                                            int64_t v, __int128 vw,
-                                            bool dec_wide) {
-  atomicAdd(&acc->cnt, 1ull);
-  if (sp.kind == DAGG_SUM_INT || sp.kind == DAGG_SUM_DEC) {
-    if (ext)
-      atomic_add_i256(&acc->sum_lo, &acc->sum_hi, ext,
-                      dec_wide ? vw : (__int128)v);
-    else if (dec_wide)
-      return false;
-    else
-      atomic_add_i128(&acc->sum_lo, &acc->sum_hi, v);
-  } else if (sp.kind == DAGG_MAX_INT || sp.kind == DAGG_MIN_INT) {
-    atomicMax(&acc->sum_lo, d_fold_xform(sp.kind, v, sp.col_unsigned));
-  }
-  return true;
-}
-
-/* epilogue: merge the block's LDS pre-aggregation table into the global one */
-template <int NAGGS>
-__device__ static inline void d_hash_lds_flush(const ScanPlan &plan,
-                                               const HashAggTable &ht,
-                                               const long long *lkeys,
-                                               const SimpleAggAcc *laccs,
-                                               uint32_t lslots) {
-  const uint32_t na = min((uint32_t)plan.n_aggs, (uint32_t)NAGGS);
-  for (uint32_t s = threadIdx.x; s < lslots; s += blockDim.x) {
-    long long key = lkeys[s];
-    if (key == (long long)0x8000000000000000ll) continue;
-    HashSlot gs = d_hash_global_slot(ht, plan.table_size, na, key);
-    if (!gs.acc) continue;
-    #pragma unroll
-    for (int a = 0; a < NAGGS; a++) {
-      if ((uint32_t)a >= na) continue;
-      const SimpleAggAcc la = laccs[s * na + a];
-      const int32_t kind = plan.aggs[a].kind;
-      if (la.cnt) atomicAdd(&gs.acc[a].cnt, la.cnt);
-      if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT) {
-        if (la.sum_lo) atomicMax(&gs.acc[a].sum_lo, la.sum_lo);
-        continue;
-      }
-      if (la.sum_lo | la.sum_hi) {
-        if (gs.ext) {
-          atomic_add_i256(&gs.acc[a].sum_lo, &gs.acc[a].sum_hi,
-                          gs.ext + a * 2,
-                          (__int128)(((unsigned __int128)la.sum_hi << 64) |
-                                     la.sum_lo));
-        } else {
-          unsigned long long old = atomicAdd(&gs.acc[a].sum_lo, la.sum_lo);
-          long long carry = (old + la.sum_lo < old) ? 1 : 0;
-          long long hi_add = (long long)la.sum_hi + carry;
-          if (hi_add) atomicAdd(&gs.acc[a].sum_hi, (unsigned long long)hi_add);
-        }
-      }
-    }
-  }
-}
+/* ---------------- hash aggregation over column planes -------- */
 
 /* sum(decimal) channel: what AggColView carries for the column. CH_DEC = v is
  * the cell's scaled value (an i128 for a 19..38-digit cell, CH_WIDE) with
@@ -3485,12 +3019,7 @@ k_plane_hash(ScanPlan plan, PlaneSet ps, HashAggTable ht,
   long long *lkeys = (long long *)lds;
   SimpleAggAcc *laccs = (SimpleAggAcc *)(lkeys + LSLOTS);
   const uint32_t na = min((uint32_t)plan.n_aggs, (uint32_t)NAGGS);
-  for (uint32_t s = threadIdx.x; s < LSLOTS; s += 256u) {
-    lkeys[s] = (long long)0x8000000000000000ll;
-    #pragma unroll
-    for (int a = 0; a < NAGGS; a++)
-      if ((uint32_t)a < na) laccs[s * na + a] = SimpleAggAcc{0, 0, 0};
-  }
+  d_hash_lds_init<NAGGS>(plan, lkeys, laccs, LSLOTS);
   __syncthreads();
   bool any_parse_err = false;
 
@@ -3589,25 +3118,11 @@ k_plane_hash(ScanPlan plan, PlaneSet ps, HashAggTable ht,
               d_filter2_keep(plan, (f2.fl & CH_FOUND) != 0,
                              (f2.fl & CH_NULL) != 0, f2.v)))
           continue;
-        /* conservative wide-decimal pre-pass: a row that may need a 256-bit
-           add must take a global slot (the LDS table is 128-bit) */
-        bool row_wide = false;
-        #pragma unroll
-        for (int a = 0; a < NAGGS; a++) {
-          if (plan.aggs[a].kind != DAGG_SUM_DEC ||
-              (ag[a].fl & (CH_FOUND | CH_NULL)) != CH_FOUND)
-            continue;
-          if (ag[a].fl & CH_WIDE) { row_wide = true; continue; }
-          if (!(ag[a].fl & CH_DEC)) continue;
-          int d = plan.aggs[a].target_frac - dg[a].frac;
-          if (d > 18) { row_wide = true; continue; }
-          if (d > 0) {
-            int64_t lim = (int64_t)(0x7FFFFFFFFFFFFFFFll);
-            for (int t = 0; t < d; t++) lim /= 10;
-            const int64_t sc = (int64_t)dg[a].v;
-            if (sc > lim || sc < -lim) row_wide = true;
-          }
-        }
+        const bool row_wide = d_row_wide<NAGGS>(plan, [&](int a) {
+          return DecIn{(ag[a].fl & (CH_FOUND | CH_NULL)) == CH_FOUND,
+                       (ag[a].fl & CH_WIDE) != 0, (ag[a].fl & CH_DEC) != 0,
+                       (int64_t)dg[a].v, dg[a].frac};
+        });
         HashSlot hs = d_hash_row_slot(
             ht, plan.table_size, na, (g.fl & CH_FOUND) != 0,
             (g.fl & CH_NULL) != 0, g.v, row_wide, lkeys, laccs, LSLOTS);
@@ -3621,31 +3136,20 @@ k_plane_hash(ScanPlan plan, PlaneSet ps, HashAggTable ht,
           if (sp.kind != DAGG_COUNT_ROWS) {
             if ((ag[a].fl & (CH_FOUND | CH_NULL)) != CH_FOUND) continue;
             if (sp.kind == DAGG_SUM_DEC) {
-              const bool okd = (ag[a].fl & CH_DEC) != 0;
-              int d = okd ? sp.target_frac - dg[a].frac : -1;
-              if (d < 0 || d > 38) { any_parse_err = true; continue; }
-              __int128 sv = dg[a].v;
-              const __int128 LIM =
-                  (__int128)(((unsigned __int128)~(unsigned __int128)0) >> 1) / 10;
-              bool ovf = false;
-              for (int t = 0; t < d; t++) {
-                if (sv > LIM || sv < -LIM) { ovf = true; break; }
-                sv *= 10;
-              }
-              if (ovf) { any_parse_err = true; continue; }  /* > 38 digits */
-              if (sv >= (__int128)INT64_MIN && sv <= (__int128)INT64_MAX) {
-                v = (int64_t)sv;
-              } else {
-                vw = sv;
-                dec_wide = true;
+              if (!(ag[a].fl & CH_DEC) ||
+                  !d_dec_rescale(dg[a].v, dg[a].frac, sp.target_frac, &v, &vw,
+                                 &dec_wide)) {
+                any_parse_err = true;   /* bad type, or > 38 digits */
+                continue;
               }
             } else {
               v = ag[a].v;
             }
           }
           if (hs.acc &&
-              !d_hash_update(sp, hs.acc + a, hs.ext ? hs.ext + a * 2 : nullptr,
-                             v, vw, dec_wide))
+              !d_hash_update<true>(sp, hs.acc + a,
+                                   hs.ext ? hs.ext + a * 2 : nullptr, v, vw,
+                                   dec_wide))
             any_parse_err = true;     /* no ext buffers: loud */
         }
       }
@@ -3654,7 +3158,7 @@ k_plane_hash(ScanPlan plan, PlaneSet ps, HashAggTable ht,
 
   if (LSLOTS) {
     __syncthreads();
-    d_hash_lds_flush<NAGGS>(plan, ht, lkeys, laccs, LSLOTS);
+    d_hash_lds_flush<NAGGS, true>(plan, ht, lkeys, laccs, LSLOTS);
   }
   if (any_parse_err) atomicOr(ht.error + 1, 1u);
 }
@@ -5361,12 +4865,12 @@ int dev_chunk_encode(const ProjectOut &po, const DevRegion &rgn, int idxp,
 }
 
 /* ---------------- launch wrappers ---------------- */
-template <bool IS_HASH, int NLOADS>
+template <bool IS_HASH>
 static int launch_agg2(const ScanPlan &plan, const DevRegion &rgn,
                        SimpleAggAcc *d_simple, HashAggTable ht, hipStream_t s,
                        uint32_t grid) {
   #define CASE(N)                                                            \
-    hipLaunchKernelGGL((k_scan_agg<N, IS_HASH, NLOADS>), dim3(grid),         \
+    hipLaunchKernelGGL((k_scan_agg<N, IS_HASH>), dim3(grid),                 \
                        dim3(THREADS), plan.lds_bytes, s, plan, rgn.d_vals,   \
                        rgn.d_val_offs, rgn.n_kv, d_simple, ht)
   switch (plan.n_aggs) {
@@ -5465,10 +4969,7 @@ static int launch_agg(const ScanPlan &plan, const DevRegion &rgn,
                       uint32_t grid) {
   if (plan.use_pipe)
     return launch_agg_pipe<IS_HASH>(plan, rgn, d_simple, ht, s, grid);
-  uint32_t nl = (plan.lds_bytes + 16 * THREADS - 1) / (16 * THREADS);
-  if (nl <= 4) return launch_agg2<IS_HASH, 4>(plan, rgn, d_simple, ht, s, grid);
-  if (nl <= 9) return launch_agg2<IS_HASH, 9>(plan, rgn, d_simple, ht, s, grid);
-  return launch_agg2<IS_HASH, 16>(plan, rgn, d_simple, ht, s, grid);
+  return launch_agg2<IS_HASH>(plan, rgn, d_simple, ht, s, grid);
 }
 
 
@@ -5538,197 +5039,48 @@ k_scan_extract(ScanPlan plan, const uint8_t *__restrict__ vals,
          my_row += blockDim.x) {
       const uint8_t *vp = lds + shift + (uint32_t)(val_offs[my_row] - gbase);
       uint32_t vlen = (uint32_t)(val_offs[my_row + 1] - val_offs[my_row]);
-      bool parse_ok = true;
       const bool GBYTES = eo.ghash != nullptr;
       uint64_t g_h = 0, g_o = 0; uint32_t g_l = 0;
-      bool filt_found = false, filt_null = false; int64_t filt_v = 0;
-      bool f2_found = false, f2_null = false; int64_t f2_v = 0;
-      bool grp_found = false, grp_null = false; int64_t grp_v = 0;
-      AggColView cols[NAGGS > 0 ? NAGGS : 1];
-      #pragma unroll
-      for (int a = 0; a < NAGGS; a++) cols[a] = {false, false, false, 0, 0, 0, nullptr, 0};
-
-      if (plan.index_mode) {
-        /* vp IS the index key (extract_launch streams the key slab) */
-        int64_t hval = 0;
-        bool hfound = false;
-        parse_ok = !GBYTES &&
-                   d_index_collect<(NAGGS > 0 ? NAGGS : 1), true>(
-                       plan, vp, vlen, my_row, &filt_found, &filt_null,
-                       &filt_v, &grp_found, &grp_null, &grp_v, cols, &hval,
-                       &hfound);
-      } else
-      if (!(vlen == 0 || (vlen == 1 && vp[0] == 0))) {
-        bool dir_done = false;
-        if (plan.celldir && vp[0] != 128) {
-          const uint8_t *db = plan.celldir;
-          const uint64_t dn = plan.celldir_n;
-          uint32_t d_f = 0xFFu, d_f2 = 0xFFu, d_g = 0xFFu,
-                   d_a[NAGGS > 0 ? NAGGS : 1];
-          bool seq = false;
-          if (plan.has_filter)
-            d_f = db[(uint64_t)(plan.filter_col_id - 1) * dn + my_row];
-          if (plan.filter2_on)
-            d_f2 = db[(uint64_t)(plan.filter2_col_id - 1) * dn + my_row];
-          d_g = db[(uint64_t)(plan.group_col_id - 1) * dn + my_row];
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++) {
-            d_a[a] = 0xFFu;
-            if (plan.aggs[a].kind != DAGG_COUNT_ROWS)
-              d_a[a] = db[(uint64_t)(plan.aggs[a].col_id - 1) * dn + my_row];
-          }
-          seq = (d_f == 0xFEu) | (d_f2 == 0xFEu) | (d_g == 0xFEu);
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++) seq |= (d_a[a] == 0xFEu);
-          if (!seq) {
-            dir_done = true;
-            int64_t cid; uint32_t coff; CellView cell; uint32_t pos;
-            if (plan.has_filter && d_f != 0xFFu) {
-              pos = d_f;
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.filter_col_id) {
-                filt_found = true;
-                if (cell.is_null) filt_null = true;
-                else if (plan.filter_is_real ? cell.has_real : cell.has_int) filt_v = cell.ival;
-                else parse_ok = false;
-              } else parse_ok = false;
-            }
-            if (plan.filter2_on && d_f2 != 0xFFu) {
-              pos = d_f2;
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.filter2_col_id) {
-                f2_found = true;
-                if (cell.is_null) f2_null = true;
-                else if (plan.filter2_is_real ? cell.has_real : cell.has_int) f2_v = cell.ival;
-                else parse_ok = false;
-              } else parse_ok = false;
-            }
-            if (d_g != 0xFFu) {
-              pos = d_g;
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.group_col_id) {
-                grp_found = true;
-                if (cell.is_null) grp_null = true;
-                else if (GBYTES) {
-                  uint32_t po, plen2;
-                  if (d_compact_bytes_span(vp, vlen, coff, &po, &plen2)) {
-                    g_h = d_fnv1a(vp + po, plen2);
-                    g_o = val_offs[my_row] + po;
-                    g_l = plen2;
-                  } else parse_ok = false;
-                } else if (cell.has_int) grp_v = cell.ival;
-                else parse_ok = false;
-              } else parse_ok = false;
-            }
-            #pragma unroll
-            for (int a = 0; a < NAGGS; a++) {
-              if (plan.aggs[a].kind == DAGG_COUNT_ROWS || d_a[a] == 0xFFu)
-                continue;
-              pos = d_a[a];
-              if (next_cell(vp, vlen, &pos, &cid, &coff, &cell) &&
-                  cid == plan.aggs[a].col_id) {
-                cols[a].found = true;
-                cols[a].null = cell.is_null;
-                cols[a].iv = cell.ival;
-                cols[a].has_dec = cell.has_dec;
-                cols[a].dsc = cell.dscaled; cols[a].dfr = cell.dfrac;
-                cols[a].dwide = cell.dwide; cols[a].dwrem = cell.dwide_rem;
-                if (!cell.is_null && !cell.has_int && !cell.has_real &&
-                    !cell.has_dec && !cell.dwide)
-                  parse_ok = false;
-              } else parse_ok = false;
+      RowVals rv{};
+      AggColView cols[NAGGS > 0 ? NAGGS : 1] = {};
+      const uint8_t *db = plan.celldir;
+      const uint64_t dn = plan.celldir_n;
+      /* in index mode vp IS the index key (extract_launch streams the key
+         slab); a bytes group key is not served there */
+      bool parse_ok =
+          !(GBYTES && plan.index_mode) &&
+          d_row_collect<(NAGGS > 0 ? NAGGS : 1), true, true>(
+              plan, vp, vlen, my_row,
+              [&](int32_t, int64_t cid) -> uint32_t {
+                return (uint32_t)db[(uint64_t)(cid - 1) * dn + my_row];
+              },
+              rv, cols, GBYTES);
+      if (!GBYTES || plan.index_mode) {
+      } else if (vlen && vp[0] == 128) {
+        V2Row r2;
+        if (!parse_ok) {
+        } else if (d_v2_parse(vp, vlen, &r2)) {
+          uint32_t s2, e2;
+          int vst = d_v2_find(r2, plan.group_col_id, &s2, &e2);
+          if (vst >= 0) {
+            rv.grp_found = true;
+            if (vst == 0) rv.grp_null = true;
+            else {
+              /* v2 cells hold the raw payload already */
+              const uint8_t *pp = r2.vals + s2;
+              g_h = d_fnv1a(pp, e2 - s2);
+              g_o = val_offs[my_row] + (uint32_t)(pp - vp);
+              g_l = e2 - s2;
             }
           }
-        }
-        if (dir_done) {
-        } else if (vp[0] == 128) {
-          parse_ok = d_v2_collect<(NAGGS > 0 ? NAGGS : 1), true>(
-              plan, vp, vlen, &filt_found, &filt_null, &filt_v, &grp_found,
-              &grp_null, &grp_v, cols, /*parse_grp=*/!GBYTES,
-              &f2_found, &f2_null, &f2_v);
-          if (parse_ok && GBYTES) {
-            V2Row r2;
-            if (d_v2_parse(vp, vlen, &r2)) {
-              uint32_t s2, e2;
-              int vst = d_v2_find(r2, plan.group_col_id, &s2, &e2);
-              if (vst >= 0) {
-                grp_found = true;
-                if (vst == 0) grp_null = true;
-                else {
-                  /* v2 cells hold the raw payload already */
-                  const uint8_t *pp = r2.vals + s2;
-                  g_h = d_fnv1a(pp, e2 - s2);
-                  g_o = val_offs[my_row] + (uint32_t)(pp - vp);
-                  g_l = e2 - s2;
-                }
-              }
-            } else parse_ok = false;
-          }
-        } else {
-          uint32_t pos = 0;
-          int needed = (plan.has_filter ? 1 : 0) + (plan.filter2_on ? 1 : 0) + 1;
-          #pragma unroll
-          for (int a = 0; a < NAGGS; a++)
-            if (plan.aggs[a].kind != DAGG_COUNT_ROWS) needed++;
-          int found = 0;
-          while (pos < vlen) {
-            int64_t cell_id;
-            uint32_t cell_off;
-            CellView cell;
-            if (!next_cell(vp, vlen, &pos, &cell_id, &cell_off, &cell)) {
-              parse_ok = false;
-              break;
-            }
-            if (plan.has_filter && !filt_found &&
-                cell_id == plan.filter_col_id) {
-              filt_found = true;
-              if (cell.is_null) filt_null = true;
-              else if (plan.filter_is_real ? cell.has_real : cell.has_int) filt_v = cell.ival;
-              else parse_ok = false;
-              found++;
-            }
-            if (plan.filter2_on && !f2_found &&
-                cell_id == plan.filter2_col_id) {
-              f2_found = true;
-              if (cell.is_null) f2_null = true;
-              else if (plan.filter2_is_real ? cell.has_real : cell.has_int) f2_v = cell.ival;
-              else parse_ok = false;
-              found++;
-            }
-            if (!grp_found && cell_id == plan.group_col_id) {
-              grp_found = true;
-              if (cell.is_null) grp_null = true;
-              else if (GBYTES) {
-                uint32_t po, plen2;
-                if (d_compact_bytes_span(vp, vlen, cell_off, &po, &plen2)) {
-                  g_h = d_fnv1a(vp + po, plen2);
-                  g_o = val_offs[my_row] + po;
-                  g_l = plen2;
-                } else parse_ok = false;
-              } else if (cell.has_int) grp_v = cell.ival;
-              else parse_ok = false;
-              found++;
-            }
-            #pragma unroll
-            for (int a = 0; a < NAGGS; a++) {
-              if (plan.aggs[a].kind == DAGG_COUNT_ROWS || cols[a].found)
-                continue;
-              if (cell_id == plan.aggs[a].col_id) {
-                cols[a].found = true;
-                cols[a].null = cell.is_null;
-                cols[a].iv = cell.ival;
-                cols[a].has_dec = cell.has_dec;
-                cols[a].dsc = cell.dscaled; cols[a].dfr = cell.dfrac;
-                cols[a].dwide = cell.dwide; cols[a].dwrem = cell.dwide_rem;
-                if (!cell.is_null && !cell.has_int && !cell.has_real &&
-                    !cell.has_dec && !cell.dwide)
-                  parse_ok = false;
-                found++;
-              }
-            }
-            if (found >= needed) break;
-          }
-        }
+        } else parse_ok = false;
+      } else if (rv.grp_found && !rv.grp_null) {
+        uint32_t po, plen2;
+        if (d_compact_bytes_span(vp, vlen, rv.grp_off, &po, &plen2)) {
+          g_h = d_fnv1a(vp + po, plen2);
+          g_o = val_offs[my_row] + po;
+          g_l = plen2;
+        } else parse_ok = false;
       }
 
       uint8_t s = 0;
@@ -5739,14 +5091,15 @@ k_scan_extract(ScanPlan plan, const uint8_t *__restrict__ vals,
       if (!parse_ok) {
         any_err = true;
       } else if (bool ke = false;
-                 d_keep2(plan, filt_found, filt_null, filt_v, f2_found,
-                         f2_null, f2_v, &ke, xv0_, xn0_, xv1_, xn1_)
+                 d_keep2(plan, rv.filt_found, rv.filt_null, rv.filt_v,
+                         rv.f2_found, rv.f2_null, rv.f2_v, &ke, xv0_, xn0_,
+                         xv1_, xn1_)
                      ? true
                      : (ke ? (any_err = true, false) : false)) {
-        s = (grp_found && !grp_null) ? 2 : 1;
+        s = (rv.grp_found && !rv.grp_null) ? 2 : 1;
       }
       eo.st[my_row] = s;
-      eo.gkey[my_row] = grp_v;
+      eo.gkey[my_row] = rv.grp_v;
       if (GBYTES) {
         eo.ghash[my_row] = s == 2 ? g_h : 0;
         eo.gofs[my_row] = g_o;
