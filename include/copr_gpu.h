@@ -109,6 +109,8 @@ uint64_t    copr_engine_hash_plane_launches(const copr_engine *);
  * narrow planes built (copr_engine_plane_builds does not count them). */
 uint64_t    copr_engine_narrow_launches(const copr_engine *);
 uint64_t    copr_engine_narrow_builds(const copr_engine *);
+/* of the narrow launches, those over a split plane */
+uint64_t    copr_engine_split_launches(const copr_engine *);
 /* TopN over several order-by columns: requests served by the
  * multi-key pipeline (monotonic), and for the last of them the rows its
  * filters kept (m) and the rows that passed the primary-key candidate cut

@@ -168,6 +168,8 @@ def load_lib():
     lib.copr_engine_narrow_launches.argtypes = [C.c_void_p]
     lib.copr_engine_narrow_builds.restype = C.c_uint64
     lib.copr_engine_narrow_builds.argtypes = [C.c_void_p]
+    lib.copr_engine_split_launches.restype = C.c_uint64
+    lib.copr_engine_split_launches.argtypes = [C.c_void_p]
     lib.copr_engine_topn_multi_runs.restype = C.c_uint64
     lib.copr_engine_topn_multi_runs.argtypes = [C.c_void_p]
     lib.copr_engine_topn_last_kept.restype = C.c_uint64

@@ -101,6 +101,10 @@ extern "C" uint64_t copr_engine_narrow_builds(const copr_engine *eng) {
   return eng ? eng->narrow_builds : 0;
 }
 
+extern "C" uint64_t copr_engine_split_launches(const copr_engine *eng) {
+  return eng ? eng->split_launches : 0;
+}
+
 extern "C" uint64_t copr_engine_topn_multi_runs(const copr_engine *eng) {
   return eng ? eng->topn_multi_runs : 0;
 }
@@ -1073,6 +1077,7 @@ static bool plane_set_used(const PlaneSet &ps) {
 struct NarrowUse {
   const DevRegion::ColPlane *p = nullptr;
   NarrowFcArgs nf{};
+  SplitFcArgs sf{};                /* a split plane's form of nf */
 };
 
 static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
@@ -1135,6 +1140,10 @@ static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
                              sp.filter_col_unsigned != 0, &nf)) {
       nu->p = np;
       nu->nf = nf;
+      /* COPR_SPLIT_ALL_LO=1 (read per call): every row is resolved from both
+         halves, the split kernel's worst case; same result bytes */
+      if (np->nar_lo_off)
+        split_fc_fold(nf, getenv("COPR_SPLIT_ALL_LO") != nullptr, &nu->sf);
     }
   }
   return true;
@@ -2510,10 +2519,11 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             nuse[rg] = NarrowUse{};
           }
       }
-      uint32_t fcn_grid = 0;              /* diagnostic: cap k_plane_fcn's grid */
+      uint32_t fcn_grid = 0;   /* diagnostic: cap k_plane_fcn / _fcs' grid */
       if (const char *g = getenv("COPR_NARROW_GRID"))
         fcn_grid = (uint32_t)strtoul(g, nullptr, 10);
-      /* one-dispatch step: every region takes k_plane_fcn, so
+      /* one-dispatch step: every region takes k_plane_fcn (or,
+         on a split plane, k_plane_fcs), so
          the whole result is one count, which the last launch's last block
          hands to the pinned host word while it re-zeroes the device words.
          No memset and no copy in the steady state. */
@@ -2554,7 +2564,7 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         hipEventRecord(ev_a, eng->stream);
         for (uint32_t rg = 0; rg < n_regions; rg++) {
           const bool last = rg + 1 == n_regions;
-          int e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf,
+          int e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf, nuse[rg].sf,
                                        regions[rg]->dev.n_kv, d_cnt,
                                        COPR_FCN_SLOTS,
                                        last ? d_ticket : nullptr,
@@ -2562,6 +2572,7 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
                                        fcn_grid, eng->stream);
           eng->plane_launches++;
           eng->narrow_launches++;
+          if (nuse[rg].p->nar_lo_off) eng->split_launches++;
           if (e) {
             eng->fcn_dirty = true;
             return SET_ERR(COPR_ERR_INTERNAL, "narrow plane launch failed");
@@ -2594,11 +2605,12 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
           if (!nuse.empty() && nuse[rg].p) {
             /* a narrow region beside regions that are not: same kernel, the
                count joins the other regions' in the usual accumulator */
-            e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf,
+            e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf, nuse[rg].sf,
                                      regions[rg]->dev.n_kv, &d_acc[0].cnt, 1,
                                      nullptr, nullptr, fcn_grid, eng->stream);
             eng->plane_launches++;
             eng->narrow_launches++;
+            if (nuse[rg].p->nar_lo_off) eng->split_launches++;
           } else if (!psets.empty() && plane_set_used(psets[rg])) {
             e = dev_plane_agg_launch(sp, psets[rg], regions[rg]->dev, d_acc,
                                      eng->stream);

@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "../../include/copr_types.h"   /* scalar sig / tp enums */
-#include "plane_fold.h"                  /* CMP_*, PlaneFcArgs, NarrowFcArgs */
+#include "plane_fold.h"                  /* CMP_*, Plane/Narrow/SplitFcArgs */
 #include "topn_keys.h"                   /* TopnKey, order-key transform, cut */
 
 namespace copr {
@@ -54,9 +54,14 @@ struct DevRegion {
        per row, for a plane whose every row is PST_INT and whose value range
        fits 32 bits. Tried once, by the first filter+count request wired to
        this plane; a declined verdict (other states present, range too wide,
-       over budget, allocation failed) is remembered. */
+       over budget, allocation failed) is remembered.
+       Width 4 is stored split: n >> 16 for every row as
+       uint16_t at nar, n & 0xFFFF likewise at nar + nar_lo_off, each plane
+       with its own tail slack. n_kv x nar_w is charged either way. */
     void *nar = nullptr;           /* [n_kv] x nar_w (+ tail slack) */
     uint32_t nar_w = 0;            /* 1, 2 or 4 */
+    uint64_t nar_lo_off = 0;       /* byte offset of the low halves; 0 = the
+                                      plane is not split (widths 1 and 2) */
     int32_t nar_verdict = 0;       /* NAR_UNTRIED / NAR_DECLINED / NAR_BUILT */
     int64_t nar_base = 0;          /* signed minimum of the plane's values */
     uint64_t nar_nmax = 0;         /* max - min */
@@ -365,12 +370,14 @@ bool dev_plane_fc_shape(const ScanPlan &plan, const PlaneSet &ps,
  * d_cnt and COPR_FCN_SLOT_STRIDE words apart; their sum is the count. With a
  * non-null d_ticket the launch finalizes: its last block stores that sum to
  * *h_out (device-visible pinned host memory) and zeroes the count words and
- * *d_ticket. grid_cap 0 = the default grid. */
+ * *d_ticket. grid_cap 0 = the default grid. A split plane
+ * (width 4) takes k_plane_fcs and sf, the others k_plane_fcn<T> and nf. */
 #define COPR_FCN_SLOTS 64
 #define COPR_FCN_SLOT_STRIDE 16          /* u64 words: one 128 B line each */
 #define COPR_FCN_STATE_WORDS (COPR_FCN_SLOTS * COPR_FCN_SLOT_STRIDE + 16)
 int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
-                         uint64_t n_rows, unsigned long long *d_cnt,
+                         const SplitFcArgs &sf, uint64_t n_rows,
+                         unsigned long long *d_cnt,
                          uint32_t n_slots, unsigned int *d_ticket,
                          unsigned long long *h_out, uint32_t grid_cap,
                          void *stream);
@@ -513,6 +520,7 @@ struct copr_engine {
   uint64_t hash_plane_launches = 0;
   uint64_t narrow_launches = 0;
   uint64_t narrow_builds = 0;
+  uint64_t split_launches = 0;     /* narrow launches that took k_plane_fcs */
 };
 
 struct copr_region {

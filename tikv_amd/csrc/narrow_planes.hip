@@ -47,7 +47,7 @@ k_plane_stats(const int64_t *__restrict__ val, const uint8_t *__restrict__ st,
 
 /* one-time narrowing pass: four rows per lane, two 16 B loads and one packed
    store. The last quad may read and write up to three rows past n_rows,
-   inside both planes' tail slack. */
+   inside both planes' tail slack. Widths 1 and 2; width 4 is k_plane_split. */
 template <typename T>
 struct alignas(4 * sizeof(T)) NarrowQuad { T r[4]; };
 
@@ -66,6 +66,32 @@ k_plane_narrow(const longlong2 *__restrict__ val, uint64_t n_rows,
     o.r[2] = (T)((uint64_t)b.x - (uint64_t)base);
     o.r[3] = (T)((uint64_t)b.y - (uint64_t)base);
     out[q] = o;
+  }
+}
+
+/* width 4: the same pass with the row split into two 16-bit
+   planes, hi[row] = n >> 16 and lo[row] = n & 0xFFFF, one packed store each */
+__global__ void __launch_bounds__(256)
+k_plane_split(const longlong2 *__restrict__ val, uint64_t n_rows, int64_t base,
+              NarrowQuad<uint16_t> *__restrict__ hi,
+              NarrowQuad<uint16_t> *__restrict__ lo) {
+  const uint64_t n_quads = (n_rows + 3) >> 2;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       q < n_quads; q += stride) {
+    longlong2 a = val[2 * q], b = val[2 * q + 1];
+    const uint32_t n[4] = {(uint32_t)((uint64_t)a.x - (uint64_t)base),
+                           (uint32_t)((uint64_t)a.y - (uint64_t)base),
+                           (uint32_t)((uint64_t)b.x - (uint64_t)base),
+                           (uint32_t)((uint64_t)b.y - (uint64_t)base)};
+    NarrowQuad<uint16_t> h, l;
+    #pragma unroll
+    for (int j = 0; j < 4; j++) {
+      h.r[j] = (uint16_t)(n[j] >> 16);
+      l.r[j] = (uint16_t)n[j];
+    }
+    hi[q] = h;
+    lo[q] = l;
   }
 }
 
@@ -106,8 +132,13 @@ const DevRegion::ColPlane *dev_colplane_narrow(DevRegion &rgn, int64_t col_id,
   if (!w) return nullptr;
   const uint64_t cost = rgn.n_kv * w;
   if (rgn.plane_bytes + cost > budget_bytes) return nullptr;
+  /* a split plane is two planes of n_kv x 2 bytes, each with its own tail
+     slack, the second on a 256 B boundary */
+  const uint64_t lo_off =
+      w == 4 ? (rgn.n_kv * 2 + 2048 + 255) & ~(uint64_t)255 : 0;
   void *nar = nullptr;
-  if (hipMalloc(&nar, cost + 2048) != hipSuccess) {
+  if (hipMalloc(&nar, w == 4 ? lo_off + rgn.n_kv * 2 + 2048
+                             : cost + 2048) != hipSuccess) {
     (void)hipGetLastError();
     return nullptr;
   }
@@ -125,8 +156,9 @@ const DevRegion::ColPlane *dev_colplane_narrow(DevRegion &rgn, int64_t col_id,
                          src, rgn.n_kv, base, (NarrowQuad<uint16_t> *)nar);
       break;
     default:
-      hipLaunchKernelGGL(k_plane_narrow<uint32_t>, dim3(grid), dim3(256), 0, s,
-                         src, rgn.n_kv, base, (NarrowQuad<uint32_t> *)nar);
+      hipLaunchKernelGGL(k_plane_split, dim3(grid), dim3(256), 0, s, src,
+                         rgn.n_kv, base, (NarrowQuad<uint16_t> *)nar,
+                         (NarrowQuad<uint16_t> *)((uint8_t *)nar + lo_off));
       break;
   }
   e = hipGetLastError();
@@ -138,6 +170,7 @@ const DevRegion::ColPlane *dev_colplane_narrow(DevRegion &rgn, int64_t col_id,
   }
   p->nar = nar;
   p->nar_w = w;
+  p->nar_lo_off = lo_off;
   p->nar_base = base;
   p->nar_nmax = nmax;
   p->nar_verdict = NAR_BUILT;
@@ -146,12 +179,8 @@ const DevRegion::ColPlane *dev_colplane_narrow(DevRegion &rgn, int64_t col_id,
   return p;
 }
 
-/* Filter+count over a narrow plane. Each lane loads 16 B = 16 / sizeof(T)
- * rows, UNR loads in flight, grid-stride; the row test is the 32-bit form of
- * k_plane_fc's (narrow_fc_fold, plane_fold.h). Every row is a known int, so
- * there is no state, no ABSENT fill and no parse error. Loads are clamped to
- * the last vector and rows masked by n_rows, as in k_plane_fc; the last
- * vector may read up to 15 B into the tail slack.
+/* The tail of the filter+count kernels below: every lane of a 256-lane block
+ * brings the rows it kept.
  * The block's count goes to one of slot_mask + 1 count words, each on a
  * 128 B line of its own, chosen by block index: thousands of adds to one word
  * queue up at the end of the launch, spread over 64 they do
@@ -161,51 +190,12 @@ const DevRegion::ColPlane *dev_colplane_narrow(DevRegion &rgn, int64_t col_id,
  * collects the count words, hands the total to the host and leaves words and
  * ticket zero for the next request. Only atomics touch these words, so no
  * cache has to be written back or invalidated. */
-template <typename T>
-__global__ void __launch_bounds__(256)
-k_plane_fcn(const uint4 *__restrict__ data, uint64_t n_rows, NarrowFcArgs nf,
-            unsigned long long *__restrict__ cnt_out, uint32_t slot_mask,
-            unsigned int *__restrict__ ticket,
-            unsigned long long *__restrict__ h_out) {
-  constexpr int UNR = 4;
-  constexpr uint32_t R = 16u / sizeof(T);          /* rows per 16 B */
-  constexpr uint32_t PW = 4u / sizeof(T);          /* rows per 32-bit word */
+__device__ __forceinline__ void
+fcn_block_count(unsigned long long cnt, unsigned long long *__restrict__ cnt_out,
+                uint32_t slot_mask, unsigned int *__restrict__ ticket,
+                unsigned long long *__restrict__ h_out) {
   __shared__ unsigned long long s_cnt[4];
   __shared__ unsigned int s_last;
-  const bool inv = nf.invert != 0;
-  unsigned long long cnt = 0;
-  const uint64_t n_vec = (n_rows + R - 1) / R;
-  const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
-  for (uint64_t p0 = (uint64_t)blockIdx.x * 256u * UNR + threadIdx.x;
-       p0 < n_vec; p0 += step) {
-    uint4 v[UNR];
-    #pragma unroll
-    for (int u = 0; u < UNR; u++) {
-      uint64_t p = min(p0 + (uint64_t)u * 256u, n_vec - 1);
-      v[u] = data[p];
-    }
-    uint32_t c = 0;
-    #pragma unroll
-    for (int u = 0; u < UNR; u++) {
-      const uint64_t p = p0 + (uint64_t)u * 256u;
-      /* rows of this vector inside the plane: R except in the last vector */
-      uint32_t live = 0;
-      if (p < n_vec) {
-        const uint64_t left = n_rows - p * R;
-        live = left < R ? (uint32_t)left : R;
-      }
-      const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-      #pragma unroll
-      for (uint32_t j = 0; j < R; j++) {
-        uint32_t n = w[j / PW];
-        if (sizeof(T) < 4)
-          n = (n >> (8u * sizeof(T) * (j % PW))) & (uint32_t)(T)~(T)0;
-        const bool keep = ((n - nf.lo) <= nf.span) != inv;
-        c += (j < live && keep) ? 1u : 0u;
-      }
-    }
-    cnt += c;
-  }
   for (int off = 32; off > 0; off >>= 1)
     cnt += (unsigned long long)__shfl_down((long long)cnt, off, 64);
   if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = cnt;
@@ -249,16 +239,163 @@ k_plane_fcn(const uint4 *__restrict__ data, uint64_t n_rows, NarrowFcArgs nf,
   }
 }
 
+/* Filter+count over a narrow plane of 1 or 2 bytes per row. Each lane loads
+ * 16 B = 16 / sizeof(T) rows, UNR loads in flight, grid-stride; the row test
+ * is the 32-bit form of k_plane_fc's (narrow_fc_fold, plane_fold.h). Every
+ * row is a known int, so there is no state, no ABSENT fill and no parse
+ * error. Loads are clamped to the last vector and rows masked by n_rows, as
+ * in k_plane_fc; the last vector may read up to 15 B into the tail slack. */
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_plane_fcn(const uint4 *__restrict__ data, uint64_t n_rows, NarrowFcArgs nf,
+            unsigned long long *__restrict__ cnt_out, uint32_t slot_mask,
+            unsigned int *__restrict__ ticket,
+            unsigned long long *__restrict__ h_out) {
+  constexpr int UNR = 4;
+  constexpr uint32_t R = 16u / sizeof(T);          /* rows per 16 B */
+  constexpr uint32_t PW = 4u / sizeof(T);          /* rows per 32-bit word */
+  const bool inv = nf.invert != 0;
+  unsigned long long cnt = 0;
+  const uint64_t n_vec = (n_rows + R - 1) / R;
+  const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * 256u * UNR + threadIdx.x;
+       p0 < n_vec; p0 += step) {
+    uint4 v[UNR];
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = min(p0 + (uint64_t)u * 256u, n_vec - 1);
+      v[u] = data[p];
+    }
+    /* all four loads issue before the first is used */
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t c = 0;
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      const uint64_t p = p0 + (uint64_t)u * 256u;
+      /* rows of this vector inside the plane: R except in the last vector */
+      uint32_t live = 0;
+      if (p < n_vec) {
+        const uint64_t left = n_rows - p * R;
+        live = left < R ? (uint32_t)left : R;
+      }
+      const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+      #pragma unroll
+      for (uint32_t j = 0; j < R; j++) {
+        uint32_t n = w[j / PW];
+        if (sizeof(T) < 4)
+          n = (n >> (8u * sizeof(T) * (j % PW))) & (uint32_t)(T)~(T)0;
+        const bool keep = ((n - nf.lo) <= nf.span) != inv;
+        c += (j < live && keep) ? 1u : 0u;
+      }
+    }
+    cnt += c;
+  }
+  fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out);
+}
+
+/* Filter+count over a split plane: k_plane_fcn's shape over the
+ * high halves alone, 8 rows per 16 B load. Phase one counts the rows whose
+ * high half decides them (split_row_in's "sure") and flags the live rows it
+ * does not (maybe and not sure), one bit per row of the lane's four vectors.
+ * Phase two, entered only by a wave that holds a flagged row, loads the low
+ * halves of the flagged vectors (same index, same clamp), all of them before
+ * the first is used, and puts the flagged rows through the full test. Rows at
+ * or beyond n_rows are never flagged: the tail slack holds arbitrary bytes.
+ * With every row flagged the low loads are as coalesced as the high ones and
+ * the launch reads n_rows x 4 bytes, as k_plane_fcn<uint32_t> did. */
+__global__ void __launch_bounds__(256)
+k_plane_fcs(const uint4 *__restrict__ hi, const uint4 *__restrict__ lo,
+            uint64_t n_rows, SplitFcArgs sf,
+            unsigned long long *__restrict__ cnt_out, uint32_t slot_mask,
+            unsigned int *__restrict__ ticket,
+            unsigned long long *__restrict__ h_out) {
+  constexpr int UNR = 4;
+  constexpr uint32_t R = 8;                        /* rows per 16 B */
+  const bool inv = sf.invert != 0;
+  unsigned long long cnt = 0;
+  const uint64_t n_vec = (n_rows + R - 1) / R;
+  const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * 256u * UNR + threadIdx.x;
+       p0 < n_vec; p0 += step) {
+    uint4 v[UNR];
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = min(p0 + (uint64_t)u * 256u, n_vec - 1);
+      v[u] = hi[p];
+    }
+    /* all four loads issue before the first is used */
+    __builtin_amdgcn_sched_barrier(0);
+    /* one bit per row, vector u in bits 8u .. 8u + 7 */
+    uint32_t livem = 0, maybe = 0, sure = 0;
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      const uint64_t p = p0 + (uint64_t)u * 256u;
+      uint32_t live = 0;
+      if (p < n_vec) {
+        const uint64_t left = n_rows - p * R;
+        live = left < R ? (uint32_t)left : R;
+      }
+      livem |= ((1u << live) - 1u) << (u * R);
+      const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+      #pragma unroll
+      for (uint32_t j = 0; j < R; j++) {
+        const uint32_t h = (j & 1u) ? w[j / 2] >> 16 : w[j / 2] & 0xFFFFu;
+        maybe |= (split_maybe(h, sf) ? 1u : 0u) << (u * R + j);
+        sure |= (split_sure(h, sf) ? 1u : 0u) << (u * R + j);
+      }
+    }
+    uint32_t in = __popc(sure & livem);
+    const uint32_t amb = maybe & ~sure & livem;
+    const unsigned long long open_lanes =
+        __builtin_amdgcn_ballot_w64(amb != 0);
+    if (open_lanes != 0) {
+      uint4 lv[UNR];
+      if (__popcll(open_lanes) >= 16) {
+        /* dense (wave-uniform): a quarter of the wave holds an open row, so
+           every lane loads its four vectors, unpredicated and coalesced */
+        #pragma unroll
+        for (int u = 0; u < UNR; u++)
+          lv[u] = lo[min(p0 + (uint64_t)u * 256u, n_vec - 1)];
+      } else {
+        #pragma unroll
+        for (int u = 0; u < UNR; u++) {
+          lv[u] = make_uint4(0, 0, 0, 0);
+          if ((amb >> (u * R)) & 0xFFu)
+            lv[u] = lo[min(p0 + (uint64_t)u * 256u, n_vec - 1)];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      uint32_t full = 0;
+      #pragma unroll
+      for (int u = 0; u < UNR; u++) {
+        const uint32_t wh[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+        const uint32_t wl[4] = {lv[u].x, lv[u].y, lv[u].z, lv[u].w};
+        #pragma unroll
+        for (uint32_t j = 0; j < R; j++) {
+          const uint32_t h = (j & 1u) ? wh[j / 2] >> 16 : wh[j / 2] & 0xFFFFu;
+          const uint32_t l = (j & 1u) ? wl[j / 2] >> 16 : wl[j / 2] & 0xFFFFu;
+          full |= (split_full_in(h, l, sf) ? 1u : 0u) << (u * R + j);
+        }
+      }
+      in += __popc(full & amb);
+    }
+    cnt += inv ? __popc(livem) - in : in;
+  }
+  fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out);
+}
+
 int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
-                         uint64_t n_rows, unsigned long long *d_cnt,
+                         const SplitFcArgs &sf, uint64_t n_rows,
+                         unsigned long long *d_cnt,
                          uint32_t n_slots, unsigned int *d_ticket,
                          unsigned long long *h_out, uint32_t grid_cap,
                          void *stream) {
   if (!p.nar || (d_ticket && !h_out) || !n_slots || n_slots > 64 ||
-      (n_slots & (n_slots - 1)))
+      (n_slots & (n_slots - 1)) || (p.nar_w == 4) != (p.nar_lo_off != 0))
     return -1;
   hipStream_t s = (hipStream_t)stream;
-  const uint32_t rows_per_vec = 16u / p.nar_w;
+  /* a split plane streams its 2-byte high halves */
+  const uint32_t rows_per_vec = p.nar_lo_off ? 8u : 16u / p.nar_w;
   const uint64_t n_vec = (n_rows + rows_per_vec - 1) / rows_per_vec;
   /* 2048 blocks = 8 per CU, each lane with 4 x 16 B in flight; a finalizing
      launch needs at least one block even over no rows */
@@ -278,8 +415,9 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
                          0, s, data, n_rows, nf, d_cnt, mask, d_ticket, h_out);
       break;
     case 4:
-      hipLaunchKernelGGL(k_plane_fcn<uint32_t>, dim3((uint32_t)nb), dim3(256),
-                         0, s, data, n_rows, nf, d_cnt, mask, d_ticket, h_out);
+      hipLaunchKernelGGL(k_plane_fcs, dim3((uint32_t)nb), dim3(256), 0, s, data,
+                         (const uint4 *)((const uint8_t *)p.nar + p.nar_lo_off),
+                         n_rows, sf, d_cnt, mask, d_ticket, h_out);
       break;
     default:
       return -1;

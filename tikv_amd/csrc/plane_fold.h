@@ -82,5 +82,72 @@ inline bool narrow_fc_fold(const PlaneFcArgs &fa, int64_t base, uint64_t nmax,
   return true;
 }
 
+/* k_plane_fcs: a 4-byte narrow plane is stored as two 16-bit
+   planes, h = n >> 16 and l = n & 0xFFFF, and the kernel streams h alone.
+   With the narrow test a <= n <= b (a = lo, b = lo + span):
+     maybe = h in [a >> 16, b >> 16]; a row outside it fails the test;
+     sure  = maybe shrunk to the h whose every l passes the test;
+   only a row in maybe and not in sure needs its l. Both are range tests in
+   32-bit unsigned arithmetic, (h - x_lo) <= x_span; an empty sure interval is
+   {0x10000, 0}, false for every h <= 0xFFFF. */
+struct SplitFcArgs {
+  uint32_t lo, span, invert;       /* the full test, as NarrowFcArgs */
+  uint32_t maybe_lo, maybe_span;
+  uint32_t sure_lo, sure_span;
+};
+
+/* NarrowFcArgs -> SplitFcArgs. [lo, lo + span] does not wrap (narrow_fc_fold
+   guarantees it), so its "never" form, the whole range inverted, comes out as
+   sure = every h. all_lo = the measuring switch COPR_SPLIT_ALL_LO: maybe =
+   every h, sure = empty, so every row is resolved from both halves. */
+inline void split_fc_fold(const NarrowFcArgs &nf, bool all_lo,
+                          SplitFcArgs *sf) {
+  sf->lo = nf.lo;
+  sf->span = nf.span;
+  sf->invert = nf.invert;
+  const uint32_t a = nf.lo, b = nf.lo + nf.span;
+  sf->maybe_lo = a >> 16;
+  sf->maybe_span = (b >> 16) - (a >> 16);
+  const int64_t s_lo = (int64_t)(a >> 16) + ((a & 0xFFFFu) != 0 ? 1 : 0);
+  const int64_t s_hi = (int64_t)(b >> 16) - ((b & 0xFFFFu) != 0xFFFFu ? 1 : 0);
+  if (all_lo) {
+    sf->maybe_lo = 0;
+    sf->maybe_span = 0xFFFFu;
+  }
+  if (all_lo || s_lo > s_hi) {
+    sf->sure_lo = 0x10000u;
+    sf->sure_span = 0;
+  } else {
+    sf->sure_lo = (uint32_t)s_lo;
+    sf->sure_span = (uint32_t)(s_hi - s_lo);
+  }
+}
+
+#if defined(__HIP__) || defined(__HIPCC__)
+#define COPR_FOLD_HD __attribute__((host)) __attribute__((device))
+#else
+#define COPR_FOLD_HD
+#endif
+
+/* the row rule of a split plane, before invert: keep = in != invert.
+   k_plane_fcs applies the three steps in two phases, the first two to every
+   row and split_full_in to the rows they leave open. */
+COPR_FOLD_HD inline bool split_maybe(uint32_t h, const SplitFcArgs &sf) {
+  return (h - sf.maybe_lo) <= sf.maybe_span;
+}
+COPR_FOLD_HD inline bool split_sure(uint32_t h, const SplitFcArgs &sf) {
+  return (h - sf.sure_lo) <= sf.sure_span;
+}
+COPR_FOLD_HD inline bool split_full_in(uint32_t h, uint32_t l,
+                                       const SplitFcArgs &sf) {
+  return (((h << 16) | l) - sf.lo) <= sf.span;
+}
+COPR_FOLD_HD inline bool split_row_in(uint32_t h, uint32_t l,
+                                      const SplitFcArgs &sf) {
+  if (!split_maybe(h, sf)) return false;
+  if (split_sure(h, sf)) return true;
+  return split_full_in(h, l, sf);
+}
+
 }  // namespace copr
 #endif

@@ -559,6 +559,11 @@ class Engine:
         return (self._lib.copr_engine_narrow_launches(self._h),
                 self._lib.copr_engine_narrow_builds(self._h))
 
+    def split_launches(self):
+        """Narrow launches (narrow_stats()[0] counts them too) that ran over
+        a split plane, i.e. took k_plane_fcs, since the engine was created."""
+        return self._lib.copr_engine_split_launches(self._h)
+
     def topn_stats(self):
         """(runs, kept, candidates): TopN requests served by the multi-key
         pipeline since the engine was created, and for the last of them the
