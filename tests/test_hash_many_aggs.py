@@ -140,3 +140,24 @@ def test_scan_only_kinds(engine, n_aggs):
         rgn.close()
     assert r_scan == want
     assert r_dflt == want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_aggs", [5, 7])
+def test_scan_only_kinds_no_pipe(engine, n_aggs):
+    """COPR_NO_PLANES=1 COPR_NO_PIPE=1: the single-buffer k_scan_agg<.., true>,
+    the kernel that serves rows too long for the pipeline, == oracle"""
+    raw = raw_rows(False)
+    req = req_of(scan_aggs(n_aggs))
+    want = _norm(_oracle(req, raw), n_aggs + 1)
+    assert want[0] == "ok" and want[2] == N_GROUPS
+    rgn = engine.region_raw(*raw[:5])
+    try:
+        h0 = engine.hash_plane_launches()
+        with env(COPR_NO_PLANES="1", COPR_NO_PIPE="1",
+                 COPR_PLANE_BUDGET_MB="64"):
+            r_nopipe = _norm(_run(engine, req, [rgn]), n_aggs + 1)
+        assert engine.hash_plane_launches() == h0
+    finally:
+        rgn.close()
+    assert r_nopipe == want

@@ -106,6 +106,29 @@ def test_row_counts(engine, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 65, 1025])
+def test_row_counts_no_pipe(engine, n):
+    """COPR_NO_PIPE=1 beside COPR_NO_PLANES=1: the single-buffer
+    k_scan_agg<1, false> gives the bytes of the pipelined scan leg"""
+    raw = width_raw(n)
+    rgn = open_region(engine, raw)
+    try:
+        for off, c in ((0, 7), (1, -1000), (2, 123456789)):
+            req = count_req(COLS3, lt(off, c))
+            with env(COPR_NO_PLANES="1", COPR_NO_PIPE=None,
+                     COPR_PLANE_BUDGET_MB="64"):
+                r_scan = _run(engine, req, [rgn])
+            with env(COPR_NO_PLANES="1", COPR_NO_PIPE="1",
+                     COPR_PLANE_BUDGET_MB="64"):
+                r_nopipe = _run(engine, req, [rgn])
+            assert r_scan[0] == "ok"
+            assert r_nopipe == r_scan
+            assert r_nopipe == _oracle(req, raw)
+    finally:
+        rgn.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("n,off,grid", [(8193, 2, "2"), (8193, 1, "1"),
                                         (16385, 0, "1")])
 def test_one_row_past_a_grid_stride_step(engine, n, off, grid):

@@ -1675,24 +1675,19 @@ static copr_status build_plan(const CoprDagRequest *req, HostPlan *pl) {
  * keeps >=2 blocks/CU of occupancy on the 160 KiB LDS). */
 static void pick_tiling(const DevRegion &rgn, ScanPlan *sp,
                         bool force_nopipe = false, uint32_t extra_lds = 0) {
-  sp->diag_stage_only = getenv("COPR_DIAG_STAGE_ONLY") ? 1 : 0;
   sp->use_pipe = 0;
-  sp->glds_nt = getenv("COPR_GLDS_NT") ? 1 : 0;
   uint32_t per_row = (sp->index_mode ? rgn.max_key_bytes : rgn.max_row_bytes) + 1;
 
   if (!force_nopipe && !getenv("COPR_NO_PIPE")) {
     /* glds double-buffer pipeline: 2 x (offs slab + vals slab [+ dir
        slabs]), 1 KiB granular. >= 2 blocks/CU needs <= ~78 KiB.
        extra_lds (e.g. the hash pre-agg table) eats into the budget. */
-    uint32_t nslabs = getenv("COPR_NO_DIR_SLAB") ? 0u
-                      : (sp->n_dir_slabs ? (uint32_t)sp->n_dir_slabs
-                                         : (sp->dir_plane ? 1u : 0u));
+    uint32_t nslabs = sp->n_dir_slabs ? (uint32_t)sp->n_dir_slabs
+                                      : (sp->dir_plane ? 1u : 0u);
     uint32_t ds = nslabs * 1024u;
     uint32_t budget = 76 * 1024 + 2 * ds;
     budget = budget > extra_lds ? budget - extra_lds : 0;
-    if (const char *e = getenv("COPR_PIPE_LDS_BUDGET")) budget = (uint32_t)atoi(e);
     uint32_t rows = 1024;
-    if (const char *e = getenv("COPR_ROWS_PER_TILE")) rows = (uint32_t)atoi(e);
     while (rows > 64) {
       uint32_t os = (((rows + 1) * 8) + 1023u) & ~1023u;
       uint32_t vs = ((rows * per_row + 31u) + 1023u) & ~1023u;
@@ -1716,9 +1711,7 @@ static void pick_tiling(const DevRegion &rgn, ScanPlan *sp,
   sp->dir_slab = 0;
 
   uint32_t budget = 64 * 1024;          /* >=2 blocks/CU on 160 KiB LDS */
-  if (const char *e = getenv("COPR_LDS_BUDGET")) budget = (uint32_t)atoi(e);
   uint32_t rows = 1024;                 /* up to 4 rows per lane per tile */
-  if (const char *e = getenv("COPR_ROWS_PER_TILE")) rows = (uint32_t)atoi(e);
   while (rows > 64 && (uint64_t)rows * per_row + 96 > budget) rows /= 2;
   if ((uint64_t)rows * per_row + 96 > budget) {
     /* giant rows: single-row tiles with exact size */
@@ -2735,14 +2728,7 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             if (sp.aggs[a].kind == DAGG_SUM_REAL) any_real_sum = true;
           /* the LDS pre-agg table accumulates sums with integer atomics;
              f64-bit sums go straight to the global table's double atomics */
-          uint32_t slots = any_real_sum ? 0u : 256u;
-          if (const char *e2 = getenv("COPR_LDS_SLOTS"))
-            slots = any_real_sum ? 0u : (uint32_t)atoi(e2);
-          if (slots & (slots - 1)) {          /* probe masks need pow2 */
-            uint32_t p2 = 1;
-            while (p2 * 2 <= slots) p2 *= 2;
-            slots = p2;
-          }
+          uint32_t slots = any_real_sum ? 0u : 256u;  /* pow2: probe masks */
           uint32_t table_b =
               slots ? (16u + slots * (8 + (uint32_t)sp.n_aggs *
                                               (uint32_t)sizeof(SimpleAggAcc)))
@@ -3231,7 +3217,7 @@ extern "C" void copr_result_free(CoprSelectResult *r) {
 }
 
 /* ---------------- checksum ---------------- */
-static void build_crc_tables(uint64_t tab[16 * 256]) {
+static void build_crc_tables(uint64_t tab[8 * 256]) {
   const uint64_t POLY = 0x42F0E1EBA9EA3693ull;
   uint64_t rpoly = 0;
   for (int i = 0; i < 64; i++)
@@ -3241,8 +3227,8 @@ static void build_crc_tables(uint64_t tab[16 * 256]) {
     for (int j = 0; j < 8; j++) crc = (crc >> 1) ^ ((crc & 1) ? rpoly : 0);
     tab[i] = crc;
   }
-  /* tables 0..7 serve slice-by-8; 8..15 extend to slice-by-16 */
-  for (int t = 1; t < 16; t++)
+  /* tables 0..7: slice-by-8, all that k_crc64_reg reads */
+  for (int t = 1; t < 8; t++)
     for (int i = 0; i < 256; i++) {
       uint64_t prev = tab[(t - 1) * 256 + i];
       tab[t * 256 + i] = tab[prev & 0xFF] ^ (prev >> 8);
@@ -3255,7 +3241,7 @@ extern "C" copr_status copr_checksum(copr_engine *eng, copr_region *const *regio
   if (!eng) return SET_ERR(COPR_ERR_INVALID_REQUEST, "null engine");
   HIP_TRY(hipSetDevice(eng->device), "hipSetDevice");
   if (!eng->d_crc_tables) {
-    uint64_t tab[16 * 256];
+    uint64_t tab[8 * 256];
     build_crc_tables(tab);
     HIP_TRY(hipMalloc(&eng->d_crc_tables, sizeof(tab)), "crc tab alloc");
     HIP_TRY(hipMemcpy(eng->d_crc_tables, tab, sizeof(tab), hipMemcpyHostToDevice),

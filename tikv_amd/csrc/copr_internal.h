@@ -243,9 +243,6 @@ struct ScanPlan {
      multi-agg): host sets it only when every needed col id is in 1..16 */
   const uint8_t *celldir;
   uint64_t celldir_n;
-  /* diagnostics: 1 = stage tiles but skip the parse (bandwidth ceiling probe;
-     COPR_DIAG_STAGE_ONLY=1; results are garbage, never used in tests) */
-  int32_t diag_stage_only;
   /* tiling */
   uint32_t rows_per_tile;
   uint32_t lds_bytes;            /* dynamic LDS per block */
@@ -253,7 +250,6 @@ struct ScanPlan {
      multiples; lds_bytes = 2 * (offs_slab + vals_slab). use_pipe 0 falls
      back to the single-buffer kernel. */
   int32_t use_pipe;
-  int32_t glds_nt;               /* nt (aux=2) on the values stream */
   uint32_t offs_slab;
   uint32_t vals_slab;
   /* dir_slab = TOTAL bytes per buffer staging tile slices of needed

@@ -1838,10 +1838,6 @@ k_scan_agg(ScanPlan plan,
     uint32_t tlen = (uint32_t)(val_offs[row1] - gbase);
     __syncthreads();                    /* previous parse done: LDS free */
     uint32_t shift = stage_tile(vals, gbase, tlen, lds);
-    if (plan.diag_stage_only) {
-      if (lds[shift] == 0xA5u && threadIdx.x == 1023u) l_cnt[0]++;
-      continue;
-    }
 
     for (uint64_t my_row = row0 + threadIdx.x; my_row < row1; my_row += blockDim.x) {
       const uint8_t *vp = lds + shift + (uint32_t)(val_offs[my_row] - gbase);
@@ -1941,19 +1937,10 @@ k_scan_agg_pipe(ScanPlan plan,
     uint32_t vc = (tbytes + 1023u) >> 10;
     const uint8_t *vsrc = vals + abase;
     uint8_t *bv = b + OS;
-    if (plan.glds_nt) {
-      for (uint32_t c = wave; c < vc; c += nwaves) {
-        uint32_t off = (c << 10) + lane * 16u;
-        /* aux=2 (nt): each byte is read once by one CU (streaming) */
-        __builtin_amdgcn_global_load_lds((const uint32_t *)(vsrc + off),
-                                         (uint32_t *)(bv + off), 16, 0, 2);
-      }
-    } else {
-      for (uint32_t c = wave; c < vc; c += nwaves) {
-        uint32_t off = (c << 10) + lane * 16u;
-        __builtin_amdgcn_global_load_lds((const uint32_t *)(vsrc + off),
-                                         (uint32_t *)(bv + off), 16, 0, 0);
-      }
+    for (uint32_t c = wave; c < vc; c += nwaves) {
+      uint32_t off = (c << 10) + lane * 16u;
+      __builtin_amdgcn_global_load_lds((const uint32_t *)(vsrc + off),
+                                       (uint32_t *)(bv + off), 16, 0, 0);
     }
     /* tile slices of the needed directory planes: rpt <= 1024 bytes each =
        one 1 KiB chunk per slab (row0 is rpt-aligned, planes have tail
@@ -2012,7 +1999,6 @@ k_scan_agg_pipe(ScanPlan plan,
     uint32_t shift = (uint32_t)(gb & 15ull);
     const uint8_t *bv = b + OS;
 
-    if (!plan.diag_stage_only) {
     if (FASTFC) {
       /* specialized: one int filter column + count(*) — the cfg2 shape.
          Streaming 16-byte register window over the row: ~1 ds_read_b64 pair
@@ -2145,7 +2131,6 @@ k_scan_agg_pipe(ScanPlan plan,
           l_lo, l_hi);
     }
     }  /* FASTFC else */
-    }  /* !diag */
     bsel ^= 1;
   }
 
@@ -2161,185 +2146,6 @@ k_scan_agg_pipe(ScanPlan plan,
     else atomicOr((unsigned int *)&simple_acc[COPR_MAX_AGGS].cnt, 1u);
   }
 }
-
-
-
-/* ---------------- 3-buffer counted-wait pipeline (filter+count) ----------------
- * Keeps TWO tiles' DMA in flight while parsing a third: per tile each wave
- * issues EXACTLY KW glds (clamped duplicates pad the count), the drain is a
- * counted s_waitcnt vmcnt(2*KW) (prefetch stays in flight across the RAW
- * barrier — cdna_hip_programming §5 "what does break it" / glds-span rows),
- * and the tile bounds are read with scalar s_load so they never enter the
- * vmcnt queue. */
-__device__ static inline uint64_t s_load_u64(const uint64_t *p) {
-  /* force the (uniform) address into SGPRs so s_load always selects */
-  uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)p);
-  uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)p >> 32));
-  uint64_t addr = ((uint64_t)hi << 32) | lo;
-  uint64_t v;
-  asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)"
-               : "=s"(v) : "s"(addr));
-  return v;
-}
-
-#define THREADS3 512u
-template <int KW>
-__global__ void __launch_bounds__(THREADS3, 2)
-k_scan_fc_pipe3(ScanPlan plan,
-                const uint8_t *__restrict__ vals,
-                const uint64_t *__restrict__ val_offs, uint64_t n_rows,
-                SimpleAggAcc *__restrict__ simple_acc) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  const uint32_t rpt = plan.rows_per_tile;
-  const uint64_t n_tiles = (n_rows + rpt - 1) / rpt;
-  const uint32_t OS = plan.offs_slab;
-  const uint32_t BUFSZ = OS + plan.vals_slab;
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const uint32_t nwaves = THREADS3 / 64u;
-  const int64_t FCID = plan.filter_col_id;
-
-  unsigned long long cnt = 0;
-  bool any_parse_err = false;
-
-  /* issue EXACTLY KW glds; the buffer SLOT comes from the unclamped request
-     (a clamped duplicate must land in the future slot, never a live one) */
-  auto issue_tile = [&](uint64_t tile_req) {
-    uint8_t *b = lds + (uint32_t)(tile_req / gridDim.x % 3ull) * BUFSZ;
-    uint64_t t = min(tile_req, n_tiles - 1);
-    uint64_t row0 = t * rpt;
-    uint64_t row1 = min(row0 + rpt, n_rows);
-    uint64_t gb = s_load_u64(val_offs + row0);
-    uint64_t ge = s_load_u64(val_offs + row1);
-    const uint8_t *osrc = (const uint8_t *)(val_offs + row0);
-    uint32_t obytes = (uint32_t)((row1 - row0 + 1) * 8);
-    uint32_t oc = (obytes + 1023u) >> 10;
-    uint64_t abase = gb & ~15ull;
-    uint32_t tbytes = (uint32_t)(ge - abase);
-    uint32_t vc = (tbytes + 1023u) >> 10;
-    const uint8_t *vsrc = vals + abase;
-    uint8_t *bv = b + OS;
-    uint32_t vc_last = vc ? vc - 1 : 0;
-    #pragma unroll
-    for (int j = 0; j < KW; j++) {
-      uint32_t c = wave + (uint32_t)j * nwaves;
-      if (c < oc) {
-        uint32_t off = (c << 10) + lane * 16u;
-        __builtin_amdgcn_global_load_lds((const uint32_t *)(osrc + off),
-                                         (uint32_t *)(b + off), 16, 0, 0);
-      } else {
-        uint32_t cv = min(c - oc, vc_last);
-        uint32_t off = (cv << 10) + lane * 16u;
-        __builtin_amdgcn_global_load_lds((const uint32_t *)(vsrc + off),
-                                         (uint32_t *)(bv + off), 16, 0, 0);
-      }
-    }
-  };
-
-  uint64_t tile = blockIdx.x;
-  if (tile >= n_tiles) return;
-  issue_tile(tile);
-  issue_tile(tile + gridDim.x);
-
-  for (; tile < n_tiles; tile += gridDim.x) {
-    /* all waves done reading the buffer the next issue overwrites */
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    issue_tile(tile + 2ull * gridDim.x);
-    /* drain everything but the newest two tiles' DMA */
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * KW) : "memory");
-    __builtin_amdgcn_s_barrier();
-
-    uint8_t *b = lds + (uint32_t)(tile / gridDim.x % 3ull) * BUFSZ;
-    uint64_t row0 = tile * rpt;
-    uint64_t row1 = min(row0 + rpt, n_rows);
-    const uint64_t *loffs = (const uint64_t *)b;
-    uint64_t gb = loffs[0];
-    uint32_t shift = (uint32_t)(gb & 15ull);
-    const uint8_t *bv = b + OS;
-
-    for (uint64_t my_row = row0 + threadIdx.x; my_row < row1; my_row += blockDim.x) {
-      uint32_t r = (uint32_t)(my_row - row0);
-      uint64_t o0 = loffs[r], o1 = loffs[r + 1];
-      const uint8_t *vp = bv + shift + (uint32_t)(o0 - gb);
-      uint32_t vlen = (uint32_t)(o1 - o0);
-      bool found = false, fnull = false, ok = true;
-      int64_t fv = 0;
-      if (!(vlen == 0 || (vlen == 1 && vp[0] == 0))) {
-        uintptr_t base = (uintptr_t)vp;
-        uintptr_t wabs = ~(uintptr_t)0;
-        uint64_t wlo = 0, whi = 0;
-        uint32_t pos = 0;
-        while (pos < vlen) {
-          uintptr_t ua = base + pos;
-          if (ua - wabs > 8) {
-            wabs = ua & ~(uintptr_t)7;
-            const uint64_t *q = (const uint64_t *)wabs;
-            wlo = q[0];
-            whi = q[1];
-          }
-          uint32_t sh = (uint32_t)(ua - wabs) * 8u;
-          uint64_t x;
-          if (sh == 0) x = wlo;
-          else if (sh == 64) x = whi;
-          else x = (wlo >> sh) | (whi << (64 - sh));
-          if ((x & 0xFF) != 8) { ok = false; break; }
-          uint32_t b1 = (uint32_t)(x >> 8) & 0xFF;
-          uint32_t dflag = (uint32_t)(x >> 16) & 0xFF;
-          if (b1 < 0x80 && (dflag == 8 || dflag == 9)) {
-            uint64_t m = x >> 24;
-            uint64_t stops = ~m & 0x8080808080ull;
-            if (stops) {
-              uint32_t half = b1 >> 1;
-              int64_t cid = (b1 & 1) ? (int64_t)(~(uint64_t)half) : (int64_t)half;
-              uint32_t n = ((uint32_t)__ffsll((long long)stops)) >> 3;
-              if (cid == FCID) {
-                uint64_t vm = m & ((n == 5) ? 0xFFFFFFFFFFull
-                                            : ((1ull << (8 * n)) - 1));
-                uint64_t uv = (vm & 0x7f) | ((vm >> 8) & 0x7f) << 7 |
-                              ((vm >> 16) & 0x7f) << 14 |
-                              ((vm >> 24) & 0x7f) << 21 |
-                              ((vm >> 32) & 0x7f) << 28;
-                if (dflag == 8) {
-                  uint64_t h2 = uv >> 1;
-                  fv = (uv & 1) ? (int64_t)~h2 : (int64_t)h2;
-                } else {
-                  fv = (int64_t)uv;
-                }
-                found = true;
-                break;
-              }
-              pos += 3 + n;
-              continue;
-            }
-          }
-          {
-            int64_t cid;
-            uint32_t cell_off;
-            CellView cell;
-            if (!next_cell(vp, vlen, &pos, &cid, &cell_off, &cell)) { ok = false; break; }
-            if (cid == FCID) {
-              if (cell.is_null) fnull = true;
-              else if (plan.filter_is_real ? cell.has_real : cell.has_int) fv = cell.ival;
-              else ok = false;
-              found = true;
-              break;
-            }
-          }
-        }
-      }
-      if (!ok) any_parse_err = true;
-      else if (d_filter_keep(plan, found, fnull, fv)) cnt++;
-    }
-  }
-
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  for (int off = 32; off > 0; off >>= 1)
-    cnt += (unsigned long long)__shfl_down((long long)cnt, off, 64);
-  if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(&simple_acc[0].cnt, cnt);
-  if (any_parse_err) atomicOr((unsigned int *)&simple_acc[COPR_MAX_AGGS].cnt, 1u);
-}
-
-
 
 /* ---------------- cell-directory ingest ----------------
  * One-time pass at region load: per row, walk the row-v1 cells byte-wise
@@ -2481,7 +2287,7 @@ int dev_celldir_build(DevRegion &rgn, hipStream_t s) {
  * dir8 is the row's cell-directory byte for the column (0xFE when the region
  * has no directory): a hit inspects the target cell alone, 0xFF is absent,
  * 0xFE walks the row and stops at the column. Reads global memory
- * (next_cell takes generic pointers, as in k_scan_fc_direct). */
+ * (next_cell takes generic pointers). */
 enum { LOC_ABSENT = 0, LOC_CELL, LOC_ERR, LOC_V2 };
 __device__ static inline int d_col_locate(const uint8_t *vp, uint32_t vlen,
                                           uint32_t dir8, int64_t col_id,
@@ -3193,348 +2999,6 @@ int dev_plane_hash_launch(const ScanPlan &plan, const PlaneSet &ps,
   return (int)hipGetLastError();
 }
 
-/* ---------------- loader-wave ring pipeline (filter+count) ----------------
- * 512-thread block: wave 7 is a dedicated LOADER streaming 64-row slots
- * (offs chunk + value chunks) into a DEPTH-deep LDS ring with counted
- * vmcnt throttling; waves 0..6 are CONSUMERS, each parsing whole slots
- * (one row per lane). All synchronization is block-local LDS flags
- * (monotonic slot numbers), so DMA issue never couples to parse barriers —
- * the ldsdma-engine shape of cdna_hip_programming §5.6 / megakernel rows.
- * KW = glds per slot (fixed by clamped duplicates). */
-template <int KW, int DEPTH>
-__global__ void __launch_bounds__(512, 2)
-k_scan_fc_ring(ScanPlan plan,
-               const uint8_t *__restrict__ vals,
-               const uint64_t *__restrict__ val_offs, uint64_t n_rows,
-               SimpleAggAcc *__restrict__ simple_acc) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  const uint32_t SLOT_ROWS = 64;
-  const uint32_t OS = 1024;                       /* offs slab: 65*8 -> 1 chunk */
-  const uint32_t SLOT_BYTES = OS + (uint32_t)(KW - 1) * 1024u;
-  /* ring slots first, then 2*DEPTH flag words */
-  volatile uint32_t *ready = (volatile uint32_t *)(lds + DEPTH * SLOT_BYTES);
-  volatile uint32_t *consumed = ready + DEPTH;
-
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const uint64_t n_slots = (n_rows + SLOT_ROWS - 1) / SLOT_ROWS;
-  /* loader in-flight depth in slots (vmcnt immediate caps at 63) */
-  constexpr int INF = (3 * KW <= 60) ? 3 : 2;
-
-  /* init flags */
-  if (threadIdx.x < DEPTH) {
-    ready[threadIdx.x] = 0;
-    consumed[threadIdx.x] = 0;
-  }
-  __syncthreads();
-
-  unsigned long long cnt = 0;
-  bool any_parse_err = false;
-  const int64_t FCID = plan.filter_col_id;
-
-  if (wave == 7) {
-    /* ---- loader ---- */
-    uint32_t inflight = 0;
-    uint64_t j = 0;                               /* block-local slot round */
-    for (uint64_t slot = blockIdx.x; ; slot += gridDim.x, j++) {
-      bool live = slot < n_slots;
-      if (!live && inflight == 0) break;
-      if (live) {
-        uint32_t pos = (uint32_t)(j % DEPTH);
-        /* wait until the slot's previous round was consumed */
-        if (j >= DEPTH) {
-          uint32_t want = (uint32_t)(j - DEPTH + 1);
-          while (consumed[pos] < want) __builtin_amdgcn_s_sleep(8);
-        }
-        uint8_t *b = lds + pos * SLOT_BYTES;
-        uint64_t row0 = slot * SLOT_ROWS;
-        uint64_t row1 = min(row0 + SLOT_ROWS, n_rows);
-        uint64_t gb = s_load_u64(val_offs + row0);
-        uint64_t ge = s_load_u64(val_offs + row1);
-        const uint8_t *osrc = (const uint8_t *)(val_offs + row0);
-        uint64_t abase = gb & ~15ull;
-        uint32_t vc = ((uint32_t)(ge - abase) + 1023u) >> 10;
-        uint32_t vc_last = vc ? vc - 1 : 0;
-        const uint8_t *vsrc = vals + abase;
-        uint8_t *bv = b + OS;
-        /* KW glds: chunk 0 = offs, 1..KW-1 = value chunks (clamped) */
-        __builtin_amdgcn_global_load_lds((const uint32_t *)(osrc + lane * 16u),
-                                         (uint32_t *)(b + lane * 16u), 16, 0, 0);
-        #pragma unroll
-        for (int c = 0; c < KW - 1; c++) {
-          uint32_t cv = min((uint32_t)c, vc_last);
-          uint32_t off = (cv << 10) + lane * 16u;
-          __builtin_amdgcn_global_load_lds((const uint32_t *)(vsrc + off),
-                                           (uint32_t *)(bv + off), 16, 0, 0);
-        }
-        inflight++;
-      }
-      /* drain to <= INF slots in flight (or everything on the tail) */
-      if (inflight > (uint32_t)INF || (!live && inflight)) {
-        if (live) {
-          asm volatile("s_waitcnt vmcnt(%0)" :: "n"(INF * KW) : "memory");
-          /* slot of round j-INF has landed */
-          uint32_t done_pos = (uint32_t)((j - INF) % DEPTH);
-          ready[done_pos] = (uint32_t)(j - INF + 1);
-          inflight--;
-        } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          while (inflight) {
-            uint32_t done_pos = (uint32_t)((j - inflight) % DEPTH);
-            ready[done_pos] = (uint32_t)(j - inflight + 1);
-            inflight--;
-          }
-        }
-      }
-    }
-  } else {
-    /* ---- consumers: wave w takes block-rounds j with j % 7 == w ---- */
-    for (uint64_t j = wave; ; j += 7) {
-      uint64_t slot = blockIdx.x + j * gridDim.x;
-      if (slot >= n_slots) break;
-      uint32_t pos = (uint32_t)(j % DEPTH);
-      uint32_t want = (uint32_t)(j + 1);
-      while (ready[pos] < want) __builtin_amdgcn_s_sleep(8);
-      asm volatile("" ::: "memory");  /* data reads stay after the flag */
-      const uint8_t *b = lds + pos * SLOT_BYTES;
-      const uint64_t *loffs = (const uint64_t *)b;
-      uint64_t row0 = slot * SLOT_ROWS;
-      uint64_t row1 = min(row0 + SLOT_ROWS, n_rows);
-      uint64_t gb = loffs[0];
-      uint32_t shift = (uint32_t)(gb & 15ull);
-      const uint8_t *bv = b + OS;
-      uint64_t my_row = row0 + lane;
-      if (my_row < row1) {
-        uint32_t dir8 = plan.dir_plane ? (uint32_t)plan.dir_plane[my_row]
-                                       : 0xFEu;
-        uint32_t r = (uint32_t)(my_row - row0);
-        uint64_t o0 = loffs[r], o1 = loffs[r + 1];
-        const uint8_t *vp = bv + shift + (uint32_t)(o0 - gb);
-        uint32_t vlen = (uint32_t)(o1 - o0);
-        bool found = false, fnull = false, ok = true;
-        int64_t fv = 0;
-        if (dir8 == 0xFFu) {
-          /* directory: filter column absent -> default fill */
-        } else if (!(vlen == 0 || (vlen == 1 && vp[0] == 0))) {
-          uintptr_t base = (uintptr_t)vp;
-          uintptr_t wabs = ~(uintptr_t)0;
-          uint64_t wlo = 0, whi = 0;
-          uint32_t posb = dir8 < 0xFEu ? dir8 : 0u;
-          while (posb < vlen) {
-            uintptr_t ua = base + posb;
-            if (ua - wabs > 8) {
-              wabs = ua & ~(uintptr_t)7;
-              const uint64_t *q = (const uint64_t *)wabs;
-              wlo = q[0];
-              whi = q[1];
-            }
-            uint32_t sh = (uint32_t)(ua - wabs) * 8u;
-            uint64_t x;
-            if (sh == 0) x = wlo;
-            else if (sh == 64) x = whi;
-            else x = (wlo >> sh) | (whi << (64 - sh));
-            if ((x & 0xFF) != 8) { ok = false; break; }
-            uint32_t b1 = (uint32_t)(x >> 8) & 0xFF;
-            uint32_t dflag = (uint32_t)(x >> 16) & 0xFF;
-            if (b1 < 0x80 && (dflag == 8 || dflag == 9)) {
-              uint64_t m = x >> 24;
-              uint64_t stops = ~m & 0x8080808080ull;
-              if (stops) {
-                uint32_t half = b1 >> 1;
-                int64_t cid = (b1 & 1) ? (int64_t)(~(uint64_t)half) : (int64_t)half;
-                uint32_t n = ((uint32_t)__ffsll((long long)stops)) >> 3;
-                if (cid == FCID) {
-                  uint64_t vm = m & ((n == 5) ? 0xFFFFFFFFFFull
-                                              : ((1ull << (8 * n)) - 1));
-                  uint64_t uv = (vm & 0x7f) | ((vm >> 8) & 0x7f) << 7 |
-                                ((vm >> 16) & 0x7f) << 14 |
-                                ((vm >> 24) & 0x7f) << 21 |
-                                ((vm >> 32) & 0x7f) << 28;
-                  if (dflag == 8) {
-                    uint64_t h2 = uv >> 1;
-                    fv = (uv & 1) ? (int64_t)~h2 : (int64_t)h2;
-                  } else {
-                    fv = (int64_t)uv;
-                  }
-                  found = true;
-                  break;
-                }
-                posb += 3 + n;
-                continue;
-              }
-            }
-            {
-              int64_t cid;
-              uint32_t cell_off;
-              CellView cell;
-              if (!next_cell(vp, vlen, &posb, &cid, &cell_off, &cell)) { ok = false; break; }
-              if (cid == FCID) {
-                if (cell.is_null) fnull = true;
-                else if (plan.filter_is_real ? cell.has_real : cell.has_int) fv = cell.ival;
-                else ok = false;
-                found = true;
-                break;
-              }
-            }
-          }
-        }
-        if (!ok) any_parse_err = true;
-        else if (d_filter_keep(plan, found, fnull, fv)) cnt++;
-      }
-      /* done with the slot: release it to the loader (whole wave writes the
-         same value — benign) */
-      if (lane == 0) consumed[pos] = want;
-    }
-  }
-
-  for (int off = 32; off > 0; off >>= 1)
-    cnt += (unsigned long long)__shfl_down((long long)cnt, off, 64);
-  if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(&simple_acc[0].cnt, cnt);
-  if (any_parse_err) atomicOr((unsigned int *)&simple_acc[COPR_MAX_AGGS].cnt, 1u);
-}
-
-/* ---------------- direct-window filter+count kernel ----------------
- * For selective scans (one int predicate column + count(*)), skip LDS
- * staging entirely: each lane loads an aligned 64 B register window at its
- * row's start and parses cells in registers. The reference's own parse
- * stops at the last requested column (table_scan_executor.rs:223), so the
- * row tail is never touched — HBM traffic drops to the touched prefix
- * cachelines. 8 waves/SIMD hide the load latency; no barriers, no LDS. */
-__global__ void __launch_bounds__(THREADS)
-k_scan_fc_direct(ScanPlan plan,
-                 const uint8_t *__restrict__ vals,
-                 const uint64_t *__restrict__ val_offs, uint64_t n_rows,
-                 SimpleAggAcc *__restrict__ simple_acc) {
-  const int64_t FCID = plan.filter_col_id;
-  unsigned long long cnt = 0;
-  bool any_err = false;
-
-  for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       row < n_rows; row += (uint64_t)gridDim.x * blockDim.x) {
-    uint64_t o0 = val_offs[row];
-    uint64_t o1 = val_offs[row + 1];
-    uint32_t vlen = (uint32_t)(o1 - o0);
-    bool found = false, fnull = false, ok = true;
-    int64_t fv = 0;
-    if (!(vlen == 0)) {
-      /* aligned 64 B register window over the row prefix */
-      const uint4 *g = (const uint4 *)(vals + (o0 & ~15ull));
-      uint4 w0 = g[0], w1 = g[1], w2 = g[2], w3 = g[3];
-      uint64_t q0 = ((uint64_t)w0.y << 32) | w0.x, q1 = ((uint64_t)w0.w << 32) | w0.z;
-      uint64_t q2 = ((uint64_t)w1.y << 32) | w1.x, q3 = ((uint64_t)w1.w << 32) | w1.z;
-      uint64_t q4 = ((uint64_t)w2.y << 32) | w2.x, q5 = ((uint64_t)w2.w << 32) | w2.z;
-      uint64_t q6 = ((uint64_t)w3.y << 32) | w3.x, q7 = ((uint64_t)w3.w << 32) | w3.z;
-      uint32_t sh0 = (uint32_t)(o0 & 15ull);
-      uint32_t wcap = 64 - sh0;                 /* window bytes available */
-      /* byte pos -> 8-byte value via a small select tree */
-      auto win8 = [&](uint32_t pos) -> uint64_t {
-        uint32_t p = sh0 + pos;
-        uint32_t i = p >> 3;
-        uint32_t sh = (p & 7u) * 8u;
-        uint64_t lo, hi;
-        switch (i) {
-          case 0: lo = q0; hi = q1; break;
-          case 1: lo = q1; hi = q2; break;
-          case 2: lo = q2; hi = q3; break;
-          case 3: lo = q3; hi = q4; break;
-          case 4: lo = q4; hi = q5; break;
-          case 5: lo = q5; hi = q6; break;
-          default: lo = q6; hi = q7; break;
-        }
-        if (sh == 0) return lo;
-        return (lo >> sh) | (hi << (64 - sh));
-      };
-      uint32_t pos = 0;
-      uint32_t first = win8(0) & 0xFF;
-      if (vlen == 1 && first == 0) {
-        /* row with no columns */
-      } else {
-        while (pos < vlen) {
-          if (pos + 8 > wcap || pos + 8 > vlen) {
-            /* window exhausted or near row end: generic global-memory path
-               for the rest of this row (rare; also covers malformed rows) */
-            const uint8_t *vp = vals + o0;
-            while (pos < vlen) {
-              int64_t cid;
-              uint32_t cell_off;
-              CellView cell;
-              if (!next_cell(vp, vlen, &pos, &cid, &cell_off, &cell)) { ok = false; break; }
-              if (cid == FCID) {
-                if (cell.is_null) fnull = true;
-                else if (plan.filter_is_real ? cell.has_real : cell.has_int) fv = cell.ival;
-                else ok = false;
-                found = true;
-                break;
-              }
-            }
-            break;
-          }
-          uint64_t x = win8(pos);
-          if ((x & 0xFF) != 8) { ok = false; break; }
-          uint32_t b1 = (uint32_t)(x >> 8) & 0xFF;
-          uint32_t dflag = (uint32_t)(x >> 16) & 0xFF;
-          if (b1 < 0x80 && (dflag == 8 || dflag == 9)) {
-            uint64_t m = x >> 24;
-            uint64_t stops = ~m & 0x8080808080ull;
-            if (stops) {
-              uint32_t half = b1 >> 1;
-              int64_t cid = (b1 & 1) ? (int64_t)(~(uint64_t)half) : (int64_t)half;
-              uint32_t n = ((uint32_t)__ffsll((long long)stops)) >> 3;
-              if (cid == FCID) {
-                uint64_t vm = m & ((n == 5) ? 0xFFFFFFFFFFull
-                                            : ((1ull << (8 * n)) - 1));
-                uint64_t uv = (vm & 0x7f) | ((vm >> 8) & 0x7f) << 7 |
-                              ((vm >> 16) & 0x7f) << 14 |
-                              ((vm >> 24) & 0x7f) << 21 |
-                              ((vm >> 32) & 0x7f) << 28;
-                if (dflag == 8) {
-                  uint64_t h2 = uv >> 1;
-                  fv = (uv & 1) ? (int64_t)~h2 : (int64_t)h2;
-                } else {
-                  fv = (int64_t)uv;
-                }
-                found = true;
-                break;
-              }
-              pos += 3 + n;
-              continue;
-            }
-          }
-          if (b1 < 0x80 && dflag == 0) {
-            uint32_t half = b1 >> 1;
-            int64_t cid = (b1 & 1) ? (int64_t)(~(uint64_t)half) : (int64_t)half;
-            if (cid == FCID) { fnull = true; found = true; break; }
-            pos += 3;
-            continue;
-          }
-          /* uncommon cell: generic parse of this one cell from global */
-          {
-            const uint8_t *vp = vals + o0;
-            int64_t cid;
-            uint32_t cell_off;
-            CellView cell;
-            if (!next_cell(vp, vlen, &pos, &cid, &cell_off, &cell)) { ok = false; break; }
-            if (cid == FCID) {
-              if (cell.is_null) fnull = true;
-              else if (plan.filter_is_real ? cell.has_real : cell.has_int) fv = cell.ival;
-              else ok = false;
-              found = true;
-              break;
-            }
-          }
-        }
-      }
-    }
-    if (!ok) any_err = true;
-    else if (d_filter_keep(plan, found, fnull, fv)) cnt++;
-  }
-
-  /* wave fold + one atomic per wave */
-  for (int off = 32; off > 0; off >>= 1)
-    cnt += (unsigned long long)__shfl_down((long long)cnt, off, 64);
-  if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(&simple_acc[0].cnt, cnt);
-  if (any_err) atomicOr((unsigned int *)&simple_acc[COPR_MAX_AGGS].cnt, 1u);
-}
-
 /* ---------------- project kernel (row-returning scans) ----------------
  * Not the hot path: dynamic out-column indexing may spill; correctness and
  * byte-identical output shape are what matter here. */
@@ -3745,11 +3209,11 @@ k_scan_project(ScanPlan plan,
   if (any_parse_err) atomicOr(po.error + 1, 1u);
 }
 
-/* ---------------- CRC-64/XZ kernels (checksum.rs:105-114) ----------------
+/* ---------------- CRC-64/XZ kernel (checksum.rs:105-114) ----------------
  * Per-KV digest over key||value, XOR-fold per wave then one atomicXor per
  * block (the running XOR is order-independent, checksum.rs:78-87).
  *
- * k_crc64_reg (default): one lane per KV, row bytes loaded from GLOBAL
+ * k_crc64_reg: one lane per KV, row bytes loaded from GLOBAL
  * memory into 8xu64 register chunks — no tile staging, no barriers. LDS
  * holds only the 16 KiB slice-by-8 tables, so 8 blocks/CU keep 8 waves/SIMD
  * of independent CRC chains in flight. The r01 tiled kernel measured 80%
@@ -3757,11 +3221,11 @@ k_scan_project(ScanPlan plan,
  * LDS-window + 8 table reads per 8 bytes has ~50-cycle dependent latency
  * per step and the stage/parse barrier phases serialized on top
  * (profiles/r02_cfg4_*). More independent chains per SIMD is the fix, not
- * more LDS bandwidth. */
-/* always_inline: with several kernels (different launch-bounds budgets)
- * calling this, hipcc otherwise OUTLINES it once sized for the tightest
- * caller — measured as 44 B/lane scratch spill and a ~2x CRC slowdown */
-template <bool PREFETCH>
+ * more LDS bandwidth. The variants that lost to it (two-row interleave,
+ * slice-by-16, no-prefetch, 6 waves/SIMD, the tiled kernel) are recorded in
+ * DESIGN.md §9b/§10. */
+/* always_inline: kept so that k_crc64_reg's code stays as measured; outlined,
+ * this function cost 44 B/lane of scratch and half the CRC throughput */
 __device__ __attribute__((always_inline)) static inline uint64_t
 d_crc64_stream(const uint8_t *__restrict__ base, uint64_t b0, uint64_t b1,
                uint64_t crc, const uint64_t *__restrict__ tab) {
@@ -3785,7 +3249,6 @@ d_crc64_stream(const uint8_t *__restrict__ base, uint64_t b0, uint64_t b1,
           tab[1 * 256 + (uint32_t)((crc >> 48) & 0xFF)] ^
           tab[0 * 256 + (uint32_t)(crc >> 56)];
   };
-  if constexpr (PREFETCH) {
   if (n8 >= 8) {
     /* software pipeline over 64-byte register chunks: chunk k+1's 8
        independent loads are in flight while the dependent table chain
@@ -3819,21 +3282,6 @@ d_crc64_stream(const uint8_t *__restrict__ base, uint64_t b0, uint64_t b1,
       step8(cur);
     }
   }
-  } else {
-    while (n8 >= 8) {
-      uint64_t w[8];
-      #pragma unroll
-      for (int j = 0; j < 8; j++) w[j] = q[wi + j];
-      #pragma unroll
-      for (int j = 0; j < 8; j++) {
-        uint64_t cur = sh ? ((prev >> sh) | (w[j] << (64 - sh))) : prev;
-        prev = w[j];
-        step8(cur);
-      }
-      wi += 8;
-      n8 -= 8;
-    }
-  }
   while (n8) {
     uint64_t w = q[wi++];
     uint64_t cur = sh ? ((prev >> sh) | (w << (64 - sh))) : prev;
@@ -3853,98 +3301,8 @@ d_crc64_stream(const uint8_t *__restrict__ base, uint64_t b0, uint64_t b1,
   return crc;
 }
 
-__device__ __attribute__((always_inline)) static inline void
-d_crc_tab8(uint64_t &crc, uint64_t cur, const uint64_t *__restrict__ tab) {
-  crc ^= cur;
-  crc = tab[7 * 256 + (uint32_t)(crc & 0xFF)] ^
-        tab[6 * 256 + (uint32_t)((crc >> 8) & 0xFF)] ^
-        tab[5 * 256 + (uint32_t)((crc >> 16) & 0xFF)] ^
-        tab[4 * 256 + (uint32_t)((crc >> 24) & 0xFF)] ^
-        tab[3 * 256 + (uint32_t)((crc >> 32) & 0xFF)] ^
-        tab[2 * 256 + (uint32_t)((crc >> 40) & 0xFF)] ^
-        tab[1 * 256 + (uint32_t)((crc >> 48) & 0xFF)] ^
-        tab[0 * 256 + (uint32_t)(crc >> 56)];
-}
-
-/* TWO-ROW interleaved variant (COPR_CRC_X2): each lane advances two
- * independent CRC chains step-for-step, so one chain's 8 dependent table
- * lookups issue under the other's latency — the single-chain kernel is
- * chain-latency-bound. Keys (tail-sized) run serially; the
- * value streams interleave in 64 B blocks and finish on the single-row
- * pipeline. */
-__global__ void __launch_bounds__(THREADS, 4)
-k_crc64_reg_x2(const uint8_t *__restrict__ vals,
-               const uint64_t *__restrict__ val_offs,
-               const uint8_t *__restrict__ keys,
-               const uint64_t *__restrict__ key_offs, uint64_t n_rows,
-               const uint64_t *__restrict__ g_tables,
-               unsigned long long *__restrict__ out_xor) {
-  __shared__ uint64_t tab[8 * 256];
-  for (uint32_t i = threadIdx.x; i < 8 * 256u; i += blockDim.x)
-    tab[i] = g_tables[i];
-  __syncthreads();
-  unsigned long long acc = 0;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  /* ADJACENT pairing: a lane's two rows sit next to each other, so the
-     wave's active span stays one contiguous window (the stride pairing
-     doubled the span and lost 17%) */
-  for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       2 * g < n_rows; g += stride) {
-    uint64_t ra = 2 * g;
-    uint64_t rb = ra + 1;
-    const bool has_b = rb < n_rows;
-    uint64_t ca = ~0ull, cb = ~0ull;
-    ca = d_crc64_stream<false>(keys, key_offs[ra], key_offs[ra + 1], ca, tab);
-    if (has_b)
-      cb = d_crc64_stream<false>(keys, key_offs[rb], key_offs[rb + 1], cb, tab);
-    uint64_t a0 = val_offs[ra], a1 = val_offs[ra + 1];
-    uint64_t b0 = has_b ? val_offs[rb] : 0;
-    uint64_t b1 = has_b ? val_offs[rb + 1] : 0;
-    const uint64_t *qa = (const uint64_t *)(vals + (a0 & ~7ull));
-    const uint64_t *qb = (const uint64_t *)(vals + (b0 & ~7ull));
-    uint32_t sha = (uint32_t)(a0 & 7) * 8u;
-    uint32_t shb = (uint32_t)(b0 & 7) * 8u;
-    uint64_t n8a = (a1 - a0) >> 3, n8b = has_b ? ((b1 - b0) >> 3) : 0;
-    uint64_t ka = 0, kb = 0;       /* 8-byte steps consumed */
-    if (n8a >= 8 && n8b >= 8) {
-      uint64_t preva = qa[0], prevb = qb[0];
-      uint64_t wia = 1, wib = 1;
-      while (n8a - ka >= 8 && n8b - kb >= 8) {
-        uint64_t wa[8], wb[8];
-        #pragma unroll
-        for (int j = 0; j < 8; j++) wa[j] = qa[wia + j];
-        #pragma unroll
-        for (int j = 0; j < 8; j++) wb[j] = qb[wib + j];
-        #pragma unroll
-        for (int j = 0; j < 8; j++) {
-          uint64_t cura = sha ? ((preva >> sha) | (wa[j] << (64 - sha)))
-                              : preva;
-          uint64_t curb = shb ? ((prevb >> shb) | (wb[j] << (64 - shb)))
-                              : prevb;
-          preva = wa[j];
-          prevb = wb[j];
-          d_crc_tab8(ca, cura, tab);
-          d_crc_tab8(cb, curb, tab);
-        }
-        wia += 8; wib += 8; ka += 8; kb += 8;
-      }
-    }
-    /* remainders (and the whole row when the partner is short) on the
-       single-row pipeline; the resume offset keeps the 8-byte phase */
-    ca = d_crc64_stream<true>(vals, a0 + ka * 8, a1, ca, tab);
-    acc ^= ~ca;
-    if (has_b) {
-      cb = d_crc64_stream<true>(vals, b0 + kb * 8, b1, cb, tab);
-      acc ^= ~cb;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1)
-    acc ^= (unsigned long long)__shfl_down((long long)acc, off, 64);
-  if ((threadIdx.x & 63u) == 0 && acc) atomicXor(out_xor, acc);
-}
-
-/* prefetch variant: 4 waves/SIMD (128 VGPRs, no spill), pipeline hides the
- * per-chunk HBM latency inside the lane */
+/* 4 waves/SIMD (128 VGPRs, no spill): d_crc64_stream's software pipeline
+ * hides the per-chunk HBM latency inside the lane */
 __global__ void __launch_bounds__(THREADS, 4)
 k_crc64_reg(const uint8_t *__restrict__ vals,
             const uint64_t *__restrict__ val_offs,
@@ -3960,276 +3318,14 @@ k_crc64_reg(const uint8_t *__restrict__ vals,
   for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
        row < n_rows; row += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t crc = ~0ull;
-    crc = d_crc64_stream<true>(keys, key_offs[row], key_offs[row + 1], crc, tab);
-    crc = d_crc64_stream<true>(vals, val_offs[row], val_offs[row + 1], crc, tab);
+    crc = d_crc64_stream(keys, key_offs[row], key_offs[row + 1], crc, tab);
+    crc = d_crc64_stream(vals, val_offs[row], val_offs[row + 1], crc, tab);
     acc ^= ~crc;
   }
   for (int off = 32; off > 0; off >>= 1)
     acc ^= (unsigned long long)__shfl_down((long long)acc, off, 64);
   if ((threadIdx.x & 63u) == 0 && acc) atomicXor(out_xor, acc);
 }
-
-/* prefetch at 6 waves/SIMD (80 VGPRs; COPR_CRC_PF6): more chains in
- * flight if the pipeline fits the tighter budget */
-__global__ void __launch_bounds__(THREADS, 6)
-k_crc64_reg_pf6(const uint8_t *__restrict__ vals,
-                const uint64_t *__restrict__ val_offs,
-                const uint8_t *__restrict__ keys,
-                const uint64_t *__restrict__ key_offs, uint64_t n_rows,
-                const uint64_t *__restrict__ g_tables,
-                unsigned long long *__restrict__ out_xor) {
-  __shared__ uint64_t tab[8 * 256];
-  for (uint32_t i = threadIdx.x; i < 8 * 256u; i += blockDim.x)
-    tab[i] = g_tables[i];
-  __syncthreads();
-  unsigned long long acc = 0;
-  for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       row < n_rows; row += (uint64_t)gridDim.x * blockDim.x) {
-    uint64_t crc = ~0ull;
-    crc = d_crc64_stream<true>(keys, key_offs[row], key_offs[row + 1], crc, tab);
-    crc = d_crc64_stream<true>(vals, val_offs[row], val_offs[row + 1], crc, tab);
-    acc ^= ~crc;
-  }
-  for (int off = 32; off > 0; off >>= 1)
-    acc ^= (unsigned long long)__shfl_down((long long)acc, off, 64);
-  if ((threadIdx.x & 63u) == 0 && acc) atomicXor(out_xor, acc);
-}
-
-/* slice-by-16 register stream (COPR_CRC_S16): one dependent table chain
- * per 16 bytes — HALF the chain steps of slice-8 — using the upper eight
- * tables the host already builds (tables 8..15 extend the slice-8 set).
- * 32 KiB of tables in LDS pair with 4 blocks/CU (128 of 160 KiB); the
- * r01 tiled kernel could not afford that because its LDS also held the
- * row tiles, which is what the COPR_CRC16 dead-end measured. */
-__device__ __attribute__((always_inline)) static inline void
-d_crc_tab16(uint64_t &crc, uint64_t lo, uint64_t hi,
-            const uint64_t *__restrict__ tab) {
-  lo ^= crc;
-  crc = tab[15 * 256 + (uint32_t)(lo & 0xFF)] ^
-        tab[14 * 256 + (uint32_t)((lo >> 8) & 0xFF)] ^
-        tab[13 * 256 + (uint32_t)((lo >> 16) & 0xFF)] ^
-        tab[12 * 256 + (uint32_t)((lo >> 24) & 0xFF)] ^
-        tab[11 * 256 + (uint32_t)((lo >> 32) & 0xFF)] ^
-        tab[10 * 256 + (uint32_t)((lo >> 40) & 0xFF)] ^
-        tab[9 * 256 + (uint32_t)((lo >> 48) & 0xFF)] ^
-        tab[8 * 256 + (uint32_t)(lo >> 56)] ^
-        tab[7 * 256 + (uint32_t)(hi & 0xFF)] ^
-        tab[6 * 256 + (uint32_t)((hi >> 8) & 0xFF)] ^
-        tab[5 * 256 + (uint32_t)((hi >> 16) & 0xFF)] ^
-        tab[4 * 256 + (uint32_t)((hi >> 24) & 0xFF)] ^
-        tab[3 * 256 + (uint32_t)((hi >> 32) & 0xFF)] ^
-        tab[2 * 256 + (uint32_t)((hi >> 40) & 0xFF)] ^
-        tab[1 * 256 + (uint32_t)((hi >> 48) & 0xFF)] ^
-        tab[0 * 256 + (uint32_t)(hi >> 56)];
-}
-
-__device__ __attribute__((always_inline)) static inline uint64_t
-d_crc64_stream16(const uint8_t *__restrict__ base, uint64_t b0, uint64_t b1,
-                 uint64_t crc, const uint64_t *__restrict__ tab) {
-  uint64_t len = b1 - b0;
-  if (!len) return crc;
-  const uint64_t *q = (const uint64_t *)(base + (b0 & ~7ull));
-  uint32_t sh = (uint32_t)(b0 & 7) * 8u;
-  uint64_t prev = q[0];
-  uint64_t wi = 1;
-  uint64_t n8 = len >> 3;
-  auto cur_of = [&](uint64_t w) {
-    uint64_t cur = sh ? ((prev >> sh) | (w << (64 - sh))) : prev;
-    prev = w;
-    return cur;
-  };
-  if (n8 >= 8) {
-    /* same 64-byte software pipeline as the slice-8 kernel, consumed in
-       16-byte table steps */
-    uint64_t w[8];
-    #pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = q[wi + j];
-    wi += 8;
-    n8 -= 8;
-    while (n8 >= 8) {
-      uint64_t w2[8];
-      #pragma unroll
-      for (int j = 0; j < 8; j++) w2[j] = q[wi + j];
-      #pragma unroll
-      for (int j = 0; j < 8; j += 2) {
-        uint64_t lo = cur_of(w[j]);
-        uint64_t hi = cur_of(w[j + 1]);
-        d_crc_tab16(crc, lo, hi, tab);
-      }
-      #pragma unroll
-      for (int j = 0; j < 8; j++) w[j] = w2[j];
-      wi += 8;
-      n8 -= 8;
-    }
-    #pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-      uint64_t lo = cur_of(w[j]);
-      uint64_t hi = cur_of(w[j + 1]);
-      d_crc_tab16(crc, lo, hi, tab);
-    }
-  }
-  while (n8 >= 2) {
-    uint64_t lo = cur_of(q[wi]);
-    uint64_t hi = cur_of(q[wi + 1]);
-    wi += 2;
-    d_crc_tab16(crc, lo, hi, tab);
-    n8 -= 2;
-  }
-  if (n8) {
-    d_crc_tab8(crc, cur_of(q[wi]), tab);
-    wi++;
-  }
-  uint32_t tail = (uint32_t)(len & 7u);
-  if (tail) {
-    uint64_t w = q[wi];
-    uint64_t cur = sh ? ((prev >> sh) | (w << (64 - sh))) : prev;
-    for (uint32_t t = 0; t < tail; t++) {
-      crc = tab[(uint32_t)((crc ^ cur) & 0xFF)] ^ (crc >> 8);
-      cur >>= 8;
-    }
-  }
-  return crc;
-}
-
-__global__ void __launch_bounds__(THREADS, 4)
-k_crc64_reg_s16(const uint8_t *__restrict__ vals,
-                const uint64_t *__restrict__ val_offs,
-                const uint8_t *__restrict__ keys,
-                const uint64_t *__restrict__ key_offs, uint64_t n_rows,
-                const uint64_t *__restrict__ g_tables,
-                unsigned long long *__restrict__ out_xor) {
-  __shared__ uint64_t tab[16 * 256];
-  for (uint32_t i = threadIdx.x; i < 16 * 256u; i += blockDim.x)
-    tab[i] = g_tables[i];
-  __syncthreads();
-  unsigned long long acc = 0;
-  for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       row < n_rows; row += (uint64_t)gridDim.x * blockDim.x) {
-    uint64_t crc = ~0ull;
-    crc = d_crc64_stream16(keys, key_offs[row], key_offs[row + 1], crc, tab);
-    crc = d_crc64_stream16(vals, val_offs[row], val_offs[row + 1], crc, tab);
-    acc ^= ~crc;
-  }
-  for (int off = 32; off > 0; off >>= 1)
-    acc ^= (unsigned long long)__shfl_down((long long)acc, off, 64);
-  if ((threadIdx.x & 63u) == 0 && acc) atomicXor(out_xor, acc);
-}
-
-/* no-prefetch variant: 8 waves/SIMD of independent chains (COPR_CRC_NP) */
-__global__ void __launch_bounds__(THREADS, 8)
-k_crc64_reg_np(const uint8_t *__restrict__ vals,
-               const uint64_t *__restrict__ val_offs,
-               const uint8_t *__restrict__ keys,
-               const uint64_t *__restrict__ key_offs, uint64_t n_rows,
-               const uint64_t *__restrict__ g_tables,
-               unsigned long long *__restrict__ out_xor) {
-  __shared__ uint64_t tab[8 * 256];
-  for (uint32_t i = threadIdx.x; i < 8 * 256u; i += blockDim.x)
-    tab[i] = g_tables[i];
-  __syncthreads();
-  unsigned long long acc = 0;
-  for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       row < n_rows; row += (uint64_t)gridDim.x * blockDim.x) {
-    uint64_t crc = ~0ull;
-    crc = d_crc64_stream<false>(keys, key_offs[row], key_offs[row + 1], crc, tab);
-    crc = d_crc64_stream<false>(vals, val_offs[row], val_offs[row + 1], crc, tab);
-    acc ^= ~crc;
-  }
-  for (int off = 32; off > 0; off >>= 1)
-    acc ^= (unsigned long long)__shfl_down((long long)acc, off, 64);
-  if ((threadIdx.x & 63u) == 0 && acc) atomicXor(out_xor, acc);
-}
-
-/* tiled LDS-staged variant (r01; COPR_CRC_TILE / COPR_CRC16 opt-in):
- * slice-by-8/16 tables + key/value tiles staged in LDS. */
-template <int NTAB>   /* 8 = slice-by-8; 16 = slice-by-16 (COPR_CRC16) */
-__global__ void __launch_bounds__(THREADS)
-k_crc64(const uint8_t *__restrict__ vals, const uint64_t *__restrict__ val_offs,
-        const uint8_t *__restrict__ keys, const uint64_t *__restrict__ key_offs,
-        uint64_t n_rows, uint32_t rows_per_tile, uint32_t key_lds_bytes,
-        const uint64_t *__restrict__ g_tables,
-        unsigned long long *__restrict__ out_xor) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  uint64_t *tab = (uint64_t *)lds;                 /* NTAB*256*8 */
-  uint8_t *key_lds = lds + NTAB * 256 * 8;
-  uint8_t *val_lds = key_lds + key_lds_bytes;
-
-  for (uint32_t i = threadIdx.x; i < NTAB * 256u; i += blockDim.x)
-    tab[i] = g_tables[i];
-
-  const uint32_t rpt = rows_per_tile;
-  const uint64_t n_tiles = (n_rows + rpt - 1) / rpt;
-  unsigned long long acc = 0;
-
-  for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    uint64_t row0 = tile * rpt;
-    uint64_t row1 = min(row0 + rpt, n_rows);
-    __syncthreads();
-    uint64_t kbase = key_offs[row0];
-    uint32_t kshift = stage_tile(keys, kbase, (uint32_t)(key_offs[row1] - kbase), key_lds);
-    uint64_t vbase = val_offs[row0];
-    uint32_t vshift = stage_tile(vals, vbase, (uint32_t)(val_offs[row1] - vbase), val_lds);
-
-    uint64_t my_row = row0 + threadIdx.x;
-    if (my_row < row1) {
-      uint64_t crc = ~0ull;
-      const uint8_t *kp = key_lds + kshift + (uint32_t)(key_offs[my_row] - kbase);
-      uint32_t klen = (uint32_t)(key_offs[my_row + 1] - key_offs[my_row]);
-      const uint8_t *vp = val_lds + vshift + (uint32_t)(val_offs[my_row] - vbase);
-      uint32_t vlen = (uint32_t)(val_offs[my_row + 1] - val_offs[my_row]);
-      /* slice-by-8 over both streams; lds_win8 keeps every 8-byte load an
-         aligned ds_read_b64 pair (a raw misaligned b64 replays 64 cycles) */
-      auto crc8 = [&](const uint8_t *p, uint32_t len, uint64_t c) {
-        uint32_t i = 0;
-        if (NTAB >= 16) {
-          /* slice-by-16: half the dependent chain length; the 16 lookups
-             per iteration are independent given c */
-          for (; i + 16 <= len; i += 16) {
-            uint64_t a = c ^ lds_win8(p + i);
-            uint64_t b = lds_win8(p + i + 8);
-            c = tab[15 * 256 + (uint32_t)(a & 0xFF)] ^
-                tab[14 * 256 + (uint32_t)((a >> 8) & 0xFF)] ^
-                tab[13 * 256 + (uint32_t)((a >> 16) & 0xFF)] ^
-                tab[12 * 256 + (uint32_t)((a >> 24) & 0xFF)] ^
-                tab[11 * 256 + (uint32_t)((a >> 32) & 0xFF)] ^
-                tab[10 * 256 + (uint32_t)((a >> 40) & 0xFF)] ^
-                tab[9 * 256 + (uint32_t)((a >> 48) & 0xFF)] ^
-                tab[8 * 256 + (uint32_t)(a >> 56)] ^
-                tab[7 * 256 + (uint32_t)(b & 0xFF)] ^
-                tab[6 * 256 + (uint32_t)((b >> 8) & 0xFF)] ^
-                tab[5 * 256 + (uint32_t)((b >> 16) & 0xFF)] ^
-                tab[4 * 256 + (uint32_t)((b >> 24) & 0xFF)] ^
-                tab[3 * 256 + (uint32_t)((b >> 32) & 0xFF)] ^
-                tab[2 * 256 + (uint32_t)((b >> 40) & 0xFF)] ^
-                tab[1 * 256 + (uint32_t)((b >> 48) & 0xFF)] ^
-                tab[0 * 256 + (uint32_t)(b >> 56)];
-          }
-        }
-        for (; i + 8 <= len; i += 8) {
-          c ^= lds_win8(p + i);
-          c = tab[7 * 256 + (uint32_t)(c & 0xFF)] ^
-              tab[6 * 256 + (uint32_t)((c >> 8) & 0xFF)] ^
-              tab[5 * 256 + (uint32_t)((c >> 16) & 0xFF)] ^
-              tab[4 * 256 + (uint32_t)((c >> 24) & 0xFF)] ^
-              tab[3 * 256 + (uint32_t)((c >> 32) & 0xFF)] ^
-              tab[2 * 256 + (uint32_t)((c >> 40) & 0xFF)] ^
-              tab[1 * 256 + (uint32_t)((c >> 48) & 0xFF)] ^
-              tab[0 * 256 + (uint32_t)(c >> 56)];
-        }
-        for (; i < len; i++)
-          c = tab[(uint32_t)((c ^ p[i]) & 0xFF)] ^ (c >> 8);
-        return c;
-      };
-      crc = crc8(kp, klen, crc);
-      crc = crc8(vp, vlen, crc);
-      acc ^= ~crc;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1)
-    acc ^= (unsigned long long)__shfl_down((long long)acc, off, 64);
-  if ((threadIdx.x & 63u) == 0 && acc) atomicXor(out_xor, acc);
-}
-
 
 /* ---------------- MVCC write-CF version filter ----------------
  * Input: sorted write-CF entries (user-key asc, commit_ts desc):
@@ -4864,112 +3960,36 @@ int dev_chunk_encode(const ProjectOut &po, const DevRegion &rgn, int idxp,
   return 0;
 }
 
-/* ---------------- launch wrappers ---------------- */
-template <bool IS_HASH>
-static int launch_agg2(const ScanPlan &plan, const DevRegion &rgn,
-                       SimpleAggAcc *d_simple, HashAggTable ht, hipStream_t s,
-                       uint32_t grid) {
-  #define CASE(N)                                                            \
-    hipLaunchKernelGGL((k_scan_agg<N, IS_HASH>), dim3(grid),                 \
-                       dim3(THREADS), plan.lds_bytes, s, plan, rgn.d_vals,   \
-                       rgn.d_val_offs, rgn.n_kv, d_simple, ht)
-  switch (plan.n_aggs) {
-    case 1: CASE(1); break;
-    case 2: CASE(2); break;
-    case 3: CASE(3); break;
-    case 4: CASE(4); break;
-    default: CASE(COPR_MAX_AGGS); break;
-  }
-  #undef CASE
-  return (int)hipGetLastError();
-}
-
-template <bool IS_HASH>
-static int launch_agg_pipe(const ScanPlan &plan, const DevRegion &rgn,
-                           SimpleAggAcc *d_simple, HashAggTable ht,
-                           hipStream_t s, uint32_t grid) {
-  if (!IS_HASH && !plan.index_mode && plan.n_aggs == 1 &&
-      plan.aggs[0].kind == DAGG_COUNT_ROWS && plan.has_filter &&
-      !plan.filter2_on && !plan.rpn_on && !plan.filter_is_real) {
-    if (getenv("COPR_DIRECT")) {
-      uint64_t n_blk = (rgn.n_kv + THREADS - 1) / THREADS;
-      uint32_t dgrid = (uint32_t)(n_blk < 8192 ? n_blk : 8192);
-      if (dgrid == 0) dgrid = 1;
-      hipLaunchKernelGGL(k_scan_fc_direct, dim3(dgrid), dim3(THREADS), 0, s,
-                         plan, rgn.d_vals, rgn.d_val_offs, rgn.n_kv, d_simple);
-      return (int)hipGetLastError();
-    }
-    if (getenv("COPR_RING")) {
-      /* KW = 1 offs chunk + value chunks for a 64-row slot */
-      uint32_t vc = ((64u * rgn.max_row_bytes + 16u) + 1023u) >> 10;
-      uint32_t kw = 1 + vc;
-      /* persistent-style grid: ~3 blocks/CU resident so each block's ring
-         reaches steady state (hundreds of rounds), not 3-4 rounds */
-      uint64_t n_slots = (rgn.n_kv + 63) / 64;
-      uint32_t rgrid = (uint32_t)min(n_slots, (uint64_t)2304);
-      if (const char *e = getenv("COPR_RING_GRID"))
-        rgrid = (uint32_t)min(n_slots, (uint64_t)atoi(e));
-      ScanPlan pr = plan;
-      #define RG(KWV, D)                                                     \
-        pr.lds_bytes = D * (1024u + (KWV - 1) * 1024u) + 2 * D * 4 + 64;     \
-        hipLaunchKernelGGL((k_scan_fc_ring<KWV, D>), dim3(rgrid), dim3(512), \
-                           pr.lds_bytes, s, pr, rgn.d_vals, rgn.d_val_offs,  \
-                           rgn.n_kv, d_simple)
-      if (kw <= 6) { RG(6, 6); return (int)hipGetLastError(); }
-      if (kw <= 10) { RG(10, 5); return (int)hipGetLastError(); }
-      if (kw <= 14) { RG(14, 4); return (int)hipGetLastError(); }
-      if (kw <= 24) { RG(24, 4); return (int)hipGetLastError(); }
-      #undef RG
-    }
-    if (getenv("COPR_PIPE3")) {
-      /* 3-buffer variant: chunks = offs + values per tile, split over 4
-         waves; KW = per-wave issue count; LDS = 3 buffers */
-      uint32_t oc = (((plan.rows_per_tile + 1) * 8) + 1023u) >> 10;
-      uint32_t vc = plan.vals_slab >> 10;
-      uint32_t kw = (oc + vc + 7u) / 8u;        /* 512-thread = 8 waves */
-      ScanPlan p3 = plan;
-      p3.lds_bytes = 3 * (plan.offs_slab + plan.vals_slab);
-      if (p3.lds_bytes <= 160 * 1024 - 2048) {
-        #define P3(KWV)                                                      \
-          hipLaunchKernelGGL((k_scan_fc_pipe3<KWV>), dim3(grid),             \
-                             dim3(512), p3.lds_bytes, s, p3, rgn.d_vals,     \
-                             rgn.d_val_offs, rgn.n_kv, d_simple)
-        if (kw <= 6) { P3(6); return (int)hipGetLastError(); }
-        if (kw <= 8) { P3(8); return (int)hipGetLastError(); }
-        if (kw <= 10) { P3(10); return (int)hipGetLastError(); }
-        if (kw <= 12) { P3(12); return (int)hipGetLastError(); }
-        if (kw <= 16) { P3(16); return (int)hipGetLastError(); }
-        if (kw <= 24) { P3(24); return (int)hipGetLastError(); }
-        #undef P3
-      }
-    }
-    hipLaunchKernelGGL((k_scan_agg_pipe<1, false, true>), dim3(grid),
-                       dim3(THREADS), plan.lds_bytes, s, plan, rgn.d_vals,
-                       rgn.d_val_offs, rgn.n_kv, d_simple, ht);
-    return (int)hipGetLastError();
-  }
-  #define CASE(N)                                                            \
-    hipLaunchKernelGGL((k_scan_agg_pipe<N, IS_HASH>), dim3(grid),            \
-                       dim3(THREADS), plan.lds_bytes, s, plan, rgn.d_vals,   \
-                       rgn.d_val_offs, rgn.n_kv, d_simple, ht)
-  switch (plan.n_aggs) {
-    case 1: CASE(1); break;
-    case 2: CASE(2); break;
-    case 3: CASE(3); break;
-    case 4: CASE(4); break;
-    default: CASE(COPR_MAX_AGGS); break;
-  }
-  #undef CASE
-  return (int)hipGetLastError();
-}
-
+/* ---------------- launch wrappers ----------------
+ * k_scan_agg and k_scan_agg_pipe take the same arguments, so one NAGGS
+ * switch picks the instance and one launch serves both. */
 template <bool IS_HASH>
 static int launch_agg(const ScanPlan &plan, const DevRegion &rgn,
                       SimpleAggAcc *d_simple, HashAggTable ht, hipStream_t s,
                       uint32_t grid) {
-  if (plan.use_pipe)
-    return launch_agg_pipe<IS_HASH>(plan, rgn, d_simple, ht, s, grid);
-  return launch_agg2<IS_HASH>(plan, rgn, d_simple, ht, s, grid);
+  void (*kern)(ScanPlan, const uint8_t *, const uint64_t *, uint64_t,
+               SimpleAggAcc *, HashAggTable);
+  if (plan.use_pipe && !IS_HASH && !plan.index_mode && plan.n_aggs == 1 &&
+      plan.aggs[0].kind == DAGG_COUNT_ROWS && plan.has_filter &&
+      !plan.filter2_on && !plan.rpn_on && !plan.filter_is_real) {
+    /* one int filter column + count(*): the specialised parse */
+    kern = k_scan_agg_pipe<1, false, true>;
+  } else {
+    #define CASE(N)                                                          \
+      kern = plan.use_pipe ? k_scan_agg_pipe<N, IS_HASH>                     \
+                           : k_scan_agg<N, IS_HASH>
+    switch (plan.n_aggs) {
+      case 1: CASE(1); break;
+      case 2: CASE(2); break;
+      case 3: CASE(3); break;
+      case 4: CASE(4); break;
+      default: CASE(COPR_MAX_AGGS); break;
+    }
+    #undef CASE
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), plan.lds_bytes, s, plan,
+                     rgn.d_vals, rgn.d_val_offs, rgn.n_kv, d_simple, ht);
+  return (int)hipGetLastError();
 }
 
 
@@ -6503,75 +5523,12 @@ int dev_scan_launch(const ScanPlan &plan, const DevRegion &rgn,
 
 int dev_crc64_launch(const DevRegion &rgn, const uint64_t *d_tables,
                      unsigned long long *d_xor, void *stream) {
-  const bool s16 = getenv("COPR_CRC16") != nullptr;
-  if (!s16 && !getenv("COPR_CRC_TILE")) {
-    /* default: register-streamed kernel (no staging) */
-    uint64_t n_blk = (rgn.n_kv + THREADS - 1) / THREADS;
-    uint32_t grid = (uint32_t)(n_blk < 8192 ? n_blk : 8192);
-    if (grid == 0) grid = 1;
-    if (getenv("COPR_CRC_NP"))
-      hipLaunchKernelGGL(k_crc64_reg_np, dim3(grid), dim3(THREADS), 0,
-                         (hipStream_t)stream, rgn.d_vals, rgn.d_val_offs,
-                         rgn.d_keys, rgn.d_key_offs, rgn.n_kv, d_tables, d_xor);
-    else if (getenv("COPR_CRC_S8"))
-      hipLaunchKernelGGL(k_crc64_reg, dim3(grid), dim3(THREADS), 0,
-                         (hipStream_t)stream, rgn.d_vals, rgn.d_val_offs,
-                         rgn.d_keys, rgn.d_key_offs, rgn.n_kv, d_tables, d_xor);
-    else if (getenv("COPR_CRC_S16"))
-      hipLaunchKernelGGL(k_crc64_reg_s16, dim3(grid), dim3(THREADS), 0,
-                         (hipStream_t)stream, rgn.d_vals, rgn.d_val_offs,
-                         rgn.d_keys, rgn.d_key_offs, rgn.n_kv, d_tables, d_xor);
-    else if (getenv("COPR_CRC_X2"))
-      hipLaunchKernelGGL(k_crc64_reg_x2, dim3(grid), dim3(THREADS), 0,
-                         (hipStream_t)stream, rgn.d_vals, rgn.d_val_offs,
-                         rgn.d_keys, rgn.d_key_offs, rgn.n_kv, d_tables, d_xor);
-    else if (getenv("COPR_CRC_PF6"))
-      hipLaunchKernelGGL(k_crc64_reg_pf6, dim3(grid), dim3(THREADS), 0,
-                         (hipStream_t)stream, rgn.d_vals, rgn.d_val_offs,
-                         rgn.d_keys, rgn.d_key_offs, rgn.n_kv, d_tables, d_xor);
-    else
-      hipLaunchKernelGGL(k_crc64_reg, dim3(grid), dim3(THREADS), 0,
-                         (hipStream_t)stream, rgn.d_vals, rgn.d_val_offs,
-                         rgn.d_keys, rgn.d_key_offs, rgn.n_kv, d_tables, d_xor);
-    return (int)hipGetLastError();
-  }
-  const uint32_t tab_b = (s16 ? 16u : 8u) * 256u * 8u;
-  uint32_t rpt = 256;
-  /* key window sized from the region's real max key length, same formula as
-     the value window (stage_tile can round the staged range up by alignment
-     shift + 16B round-up, covered by the +16/+32 slack) */
-  uint64_t max_tile_key = (uint64_t)rpt * (rgn.max_key_bytes + 16) + 32;
-  uint64_t max_tile_val = (uint64_t)rpt * (rgn.max_row_bytes + 16) + 32;
-  /* keep tables+keys+values <= ~52 KiB so >=3 blocks/CU stay resident —
-     the per-row CRC chain is latency-bound and needs wave parallelism */
-  while (rpt > 32 && tab_b + max_tile_key + max_tile_val > 52 * 1024) {
-    rpt /= 2;
-    max_tile_key = (uint64_t)rpt * (rgn.max_key_bytes + 16) + 32;
-    max_tile_val = (uint64_t)rpt * (rgn.max_row_bytes + 16) + 32;
-  }
-  while (rpt > 1 && tab_b + max_tile_key + max_tile_val > 158 * 1024) {
-    rpt /= 2;
-    max_tile_key = (uint64_t)rpt * (rgn.max_key_bytes + 16) + 32;
-    max_tile_val = (uint64_t)rpt * (rgn.max_row_bytes + 16) + 32;
-  }
-  if (tab_b + max_tile_key + max_tile_val > 160 * 1024)
-    return -2;          /* region's rows cannot fit one per tile: loud error */
-  uint32_t key_lds = (uint32_t)max_tile_key;
-  uint32_t lds_bytes = tab_b + key_lds + (uint32_t)max_tile_val;
-  uint64_t n_tiles = (rgn.n_kv + rpt - 1) / rpt;
-  uint32_t grid = (uint32_t)(n_tiles < 4096 ? n_tiles : 4096);
+  uint64_t n_blk = (rgn.n_kv + THREADS - 1) / THREADS;
+  uint32_t grid = (uint32_t)(n_blk < 8192 ? n_blk : 8192);
   if (grid == 0) grid = 1;
-  if (s16) {
-    hipLaunchKernelGGL((k_crc64<16>), dim3(grid), dim3(THREADS), lds_bytes,
-                       (hipStream_t)stream, rgn.d_vals, rgn.d_val_offs,
-                       rgn.d_keys, rgn.d_key_offs, rgn.n_kv, rpt, key_lds,
-                       d_tables, d_xor);
-    return (int)hipGetLastError();
-  }
-  hipLaunchKernelGGL((k_crc64<8>), dim3(grid), dim3(THREADS), lds_bytes,
-                     (hipStream_t)stream,
-                     rgn.d_vals, rgn.d_val_offs, rgn.d_keys, rgn.d_key_offs,
-                     rgn.n_kv, rpt, key_lds, d_tables, d_xor);
+  hipLaunchKernelGGL(k_crc64_reg, dim3(grid), dim3(THREADS), 0,
+                     (hipStream_t)stream, rgn.d_vals, rgn.d_val_offs,
+                     rgn.d_keys, rgn.d_key_offs, rgn.n_kv, d_tables, d_xor);
   return (int)hipGetLastError();
 }
 
