@@ -118,6 +118,17 @@ uint64_t    copr_engine_split_launches(const copr_engine *);
 uint64_t    copr_engine_topn_multi_runs(const copr_engine *);
 uint64_t    copr_engine_topn_last_kept(const copr_engine *);
 uint64_t    copr_engine_topn_last_candidates(const copr_engine *);
+/* Hash aggregation over two to four group-by columns:
+ * requests served by the two-stage path (monotonic); for the last of them
+ * the filled slots of its tuple dictionary (tuples seen in any row of the
+ * region, dropped rows included); dictionary doublings (monotonic); and
+ * stage-1 runs that read at least one key from the row bytes instead of a
+ * column plane (monotonic). Requests with one group-by expression move none
+ * of them. */
+uint64_t    copr_engine_group_multi_runs(const copr_engine *);
+uint64_t    copr_engine_group_last_groups(const copr_engine *);
+uint64_t    copr_engine_group_dict_grows(const copr_engine *);
+uint64_t    copr_engine_group_row_source_runs(const copr_engine *);
 
 /* ---- checksum (REQ_TYPE_CHECKSUM = 105; src/coprocessor/checksum.rs:59-114) ----
  * CRC-64/XZ per KV over key||value, XOR-folded (order-independent). */

@@ -164,7 +164,9 @@ typedef struct CoprExecutor {
   const CoprExpr *conditions;
   uint32_t        n_conditions;
   /* aggregations */
-  const CoprExpr *group_by;     /* group-by expressions */
+  const CoprExpr *group_by;     /* group-by expressions: one, or for the hash
+                                   aggregations two to four int columns
+                                    */
   uint32_t        n_group_by;
   const CoprAggDef *aggs;
   uint32_t          n_aggs;

@@ -176,6 +176,12 @@ def load_lib():
     lib.copr_engine_topn_last_kept.argtypes = [C.c_void_p]
     lib.copr_engine_topn_last_candidates.restype = C.c_uint64
     lib.copr_engine_topn_last_candidates.argtypes = [C.c_void_p]
+    for name in ("copr_engine_group_multi_runs",
+                 "copr_engine_group_last_groups",
+                 "copr_engine_group_dict_grows",
+                 "copr_engine_group_row_source_runs"):
+        getattr(lib, name).restype = C.c_uint64
+        getattr(lib, name).argtypes = [C.c_void_p]
     lib.copr_checksum.restype = C.c_int
     lib.copr_checksum.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32,
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),

@@ -113,6 +113,22 @@ extern "C" uint64_t copr_engine_topn_last_kept(const copr_engine *eng) {
   return eng ? eng->topn_last_kept : 0;
 }
 
+extern "C" uint64_t copr_engine_group_multi_runs(const copr_engine *eng) {
+  return eng ? eng->group_multi_runs : 0;
+}
+
+extern "C" uint64_t copr_engine_group_last_groups(const copr_engine *eng) {
+  return eng ? eng->group_last_groups : 0;
+}
+
+extern "C" uint64_t copr_engine_group_dict_grows(const copr_engine *eng) {
+  return eng ? eng->group_dict_grows : 0;
+}
+
+extern "C" uint64_t copr_engine_group_row_source_runs(const copr_engine *eng) {
+  return eng ? eng->group_row_source_runs : 0;
+}
+
 extern "C" uint64_t copr_engine_topn_last_candidates(const copr_engine *eng) {
   return eng ? eng->topn_last_candidates : 0;
 }
@@ -799,6 +815,12 @@ struct HostPlan {
   bool simple_as_stream = false;   /* simple agg with FIRST: one-run stream */
   bool hash_sorted = false;        /* FastHash + FIRST: sorted pipeline */
   CoprFieldType group_ft{};
+  /* several group-by columns: group_multi with the distinct key
+     columns in group_keys; group_pos[j] = the key that output group column j
+     (request order, repeats included) shows */
+  bool group_multi = false;
+  std::vector<copr::GroupKey> group_keys;
+  std::vector<int> group_pos;
   /* TopN (top_n_executor.rs): int order-by columns. One order-by
      expression: topn_off / topn_desc and dev_topn_select. Several (DESIGN
      §9f): topn_multi with the distinct keys in topn_keys. */
@@ -1082,7 +1104,7 @@ struct NarrowUse {
 
 static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
                        PlaneSet *ps, bool hash = false,
-                       NarrowUse *nu = nullptr) {
+                       NarrowUse *nu = nullptr, bool wire_group = true) {
   *ps = PlaneSet{};
   if (nu) *nu = NarrowUse{};
   if (!dev.n_kv) return false;
@@ -1092,7 +1114,8 @@ static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
   struct Want { int64_t col; PlaneRef *ref; };
   Want want[COPR_MAX_AGGS + 3];
   int n_want = 0;
-  if (hash) want[n_want++] = {sp.group_col_id, &ps->g};
+  /* wire_group false: the caller supplies ps->g (multi-key group ids) */
+  if (hash && wire_group) want[n_want++] = {sp.group_col_id, &ps->g};
   if (sp.has_filter) want[n_want++] = {sp.filter_col_id, &ps->f};
   if (sp.filter2_on) want[n_want++] = {sp.filter2_col_id, &ps->f2};
   for (int a = 0; a < sp.n_aggs; a++)
@@ -1122,7 +1145,7 @@ static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
     for (int a = 0; a < sp.n_aggs; a++) {
       const PlaneRef &r = ps->a[a];
       if (!r.val) continue;
-      if (r.val == ps->g.val) ps->a_src[a] = 1;
+      if (ps->g.val && r.val == ps->g.val) ps->a_src[a] = 1;
       else if (r.val == ps->f.val) ps->a_src[a] = 2;
       else if (r.val == ps->f2.val) ps->a_src[a] = 3;
       else
@@ -1380,9 +1403,12 @@ static copr_status build_plan(const CoprDagRequest *req, HostPlan *pl) {
         break;
       }
       case COPR_EXEC_SIMPLE_AGG: case COPR_EXEC_FAST_HASH_AGG:
+      case COPR_EXEC_SLOW_HASH_AGG:
+        /* SLOW_HASH_AGG plans as FAST_HASH_AGG does: the group-by list, not
+           the executor kind, picks the path */
         if (agg) return SET_ERR(COPR_ERR_UNSUPPORTED, "one aggregation supported");
         agg = &ex;
-        pl->hash_agg = ex.kind == COPR_EXEC_FAST_HASH_AGG;
+        pl->hash_agg = ex.kind != COPR_EXEC_SIMPLE_AGG;
         break;
       case COPR_EXEC_STREAM_AGG:
         if (agg) return SET_ERR(COPR_ERR_UNSUPPORTED, "one aggregation supported");
@@ -1626,7 +1652,68 @@ static copr_status build_plan(const CoprDagRequest *req, HostPlan *pl) {
   bool any_first = false;
   for (int a = 0; a < sp.n_aggs; a++)
     if (sp.aggs[a].kind == DAGG_FIRST) any_first = true;
-  if (pl->hash_agg) {
+  if (pl->hash_agg && agg->n_group_by > 1) {
+    /* several keys: each a COLUMN_REF to an int non-handle column of a table
+       scan; a column named twice is one key, emitted at each position */
+    if (pl->stream_agg)
+      return SET_ERR(COPR_ERR_UNSUPPORTED,
+                     "multi-key group-by: stream agg takes one group-by expr");
+    if (agg->n_group_by > COPR_GROUP_MAX_KEYS)
+      return SET_ERR(COPR_ERR_UNSUPPORTED,
+                     "multi-key group-by: at most 4 group-by expressions");
+    if (sp.index_mode)
+      return SET_ERR(COPR_ERR_UNSUPPORTED,
+                     "multi-key group-by over an index scan not yet native");
+    if (sp.rpn_on || sp.n_xcap)
+      return SET_ERR(COPR_ERR_UNSUPPORTED,
+                     "multi-key group-by supports cmp(col,const) predicates "
+                     "only (no RPN or capture-channel predicates)");
+    for (uint32_t k = 0; k < agg->n_group_by; k++) {
+      const CoprExpr &ge = agg->group_by[k];
+      if (ge.n_nodes != 1 || ge.nodes[0].kind != COPR_EXPR_COLUMN_REF)
+        return SET_ERR(COPR_ERR_UNSUPPORTED,
+                       "multi-key group-by: group-by must be a column");
+      size_t goff = (size_t)ge.nodes[0].i64_val;
+      if (goff >= pl->cols.size())
+        return SET_ERR(COPR_ERR_INVALID_REQUEST, "bad group offset");
+      const CoprColumnInfo &gc = pl->cols[goff];
+      if (gc.pk_handle)
+        return SET_ERR(COPR_ERR_UNSUPPORTED,
+                       "multi-key group-by: handle column as group key not "
+                       "yet native");
+      if (!et_int(gc.ft.tp))
+        return SET_ERR(COPR_ERR_UNSUPPORTED,
+                       "multi-key group-by: group-by type not yet native");
+      pl->out_schema.push_back(gc.ft);
+      int at = -1;
+      for (size_t q = 0; q < pl->group_keys.size(); q++)
+        if (pl->group_keys[q].col_off == (int32_t)goff) at = (int)q;
+      if (at < 0) {
+        copr::GroupKey gk{};
+        gk.col_id = gc.column_id;
+        gk.col_off = (int32_t)goff;
+        gk.uns = (gc.ft.flag & COPR_FLAG_UNSIGNED) ? 1 : 0;
+        /* absent cell: the scan's default fill, else NULL */
+        gk.missing_null = 1;
+        if (gc.default_val && gc.default_val_len) {
+          int64_t dv;
+          int r = host_decode_int_datum(gc.default_val, gc.default_val_len, &dv);
+          if (r < 0) return SET_ERR(COPR_ERR_INVALID_REQUEST, "bad default");
+          gk.missing_null = r == 1 ? 1 : 0;
+          gk.missing_val = dv;
+        }
+        at = (int)pl->group_keys.size();
+        pl->group_keys.push_back(gk);
+      }
+      pl->group_pos.push_back(at);
+    }
+    pl->group_multi = true;
+    /* stage 2 is keyed by the group id; the scan-path extract pass of the
+       sorted route still parses a group slot, and gets key 0's column */
+    sp.mode = 2;
+    sp.group_col_id = pl->group_keys[0].col_id;
+    sp.group_col_unsigned = pl->group_keys[0].uns;
+  } else if (pl->hash_agg) {
     if (agg->n_group_by != 1)
       return SET_ERR(COPR_ERR_UNSUPPORTED, "exactly one group-by expr");
     const CoprExpr &ge = agg->group_by[0];
@@ -2664,12 +2751,138 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
          events, and retries after a table-full reuse the wiring. A region
          without planes scans into the same table. */
       std::vector<PlaneSet> psets;
-      if (!getenv("COPR_NO_PLANES") && hash_plane_plan_ok(pl.sp)) {
+      if (!pl.group_multi && !getenv("COPR_NO_PLANES") &&
+          hash_plane_plan_ok(pl.sp)) {
         psets.resize(n_regions);
         for (uint32_t rg = 0; rg < n_regions; rg++)
           if (!plane_wire(eng, regions[rg]->dev, pl.sp, &psets[rg], true))
             psets[rg] = PlaneSet{};
       }
+      /* ---- several group-by columns: stage 1 turns every
+         row's key tuple into one exact group id; stage 2 is the single-key
+         machinery keyed by that id: k_plane_hash with the id buffer as its
+         group plane when the other columns wire to planes, the sorted
+         pipeline otherwise ---- */
+      GroupIds gm{};
+      struct GmGuard {
+        GroupIds *g;
+        ~GmGuard() { dev_group_free(g); }
+      } gm_guard{&gm};
+      bool gm_sorted = false;
+      /* rows for the groups named by slot index: aggregates first, then the
+         group columns in request order */
+      auto emit_multi = [&](const long long *slots, uint64_t n_groups,
+                            const SimpleAggAcc *accs,
+                            const unsigned long long *ext) -> copr_status {
+        const uint64_t take = n_groups < pl.limit ? n_groups : pl.limit;
+        std::vector<uint32_t> which(take);
+        for (uint64_t i = 0; i < take; i++) which[i] = (uint32_t)slots[i];
+        std::vector<int64_t> gv;
+        std::vector<uint8_t> gn;
+        int grc = dev_group_gather(gm, which.data(), take, eng->stream, &gv, &gn);
+        if (grc == -2) return SET_ERR(COPR_ERR_OOM, "group key gather alloc");
+        if (grc) return SET_ERR(COPR_ERR_INTERNAL, "group key gather failed");
+        const size_t n_out_cols = pl.out_schema.size();
+        const size_t g0 = n_out_cols - pl.group_pos.size();
+        const int na = pl.sp.n_aggs;
+        bool enc_err = false;
+        for (uint64_t i = 0; i < take; i++) {
+          std::vector<std::vector<uint8_t>> cols(n_out_cols);
+          encode_agg_row(pl, accs + i * na, false, false, 0, &cols,
+                         ext ? ext + i * na * 2 : nullptr, &enc_err);
+          for (size_t j = 0; j < pl.group_pos.size(); j++) {
+            const int k = pl.group_pos[j];
+            if (gn[(size_t)k * take + i]) enc_datum_null(&cols[g0 + j]);
+            else
+              enc_datum_int(&cols[g0 + j], gv[(size_t)k * take + i],
+                            pl.group_keys[k].uns != 0);
+          }
+          for (uint32_t oo = 0; oo < req->n_output_offsets; oo++) {
+            uint32_t off = req->output_offsets[oo];
+            if (off < n_out_cols)
+              resp.insert(resp.end(), cols[off].begin(), cols[off].end());
+          }
+          n_rows_out++;
+        }
+        if (enc_err)
+          return SET_ERR(COPR_ERR_STORAGE,
+                         "decimal sum overflow (Res::Overflow)");
+        return COPR_OK;
+      };
+      if (pl.group_multi) {
+        if (n_regions != 1)
+          return SET_ERR(COPR_ERR_UNSUPPORTED,
+                         "multi-key group-by supports one region per request");
+        DevRegion &dev = regions[0]->dev;
+        if (dev.n_kv >= 0xFFFFFFFFull)
+          return SET_ERR(COPR_ERR_UNSUPPORTED,
+                         "multi-key group-by: region of 2^32 - 1 rows or more");
+        const int K = (int)pl.group_keys.size();
+        const bool planes_on = !getenv("COPR_NO_PLANES");
+        /* key planes, built here (before the timed events) under the hash
+           consumer's budget; one with rows left to the row bytes or decimal
+           rows is not a key source */
+        PlaneRef kp[COPR_GROUP_MAX_KEYS] = {};
+        if (planes_on && dev.n_kv) {
+          uint64_t budget = dev.val_bytes;
+          if (const char *e = getenv("COPR_PLANE_BUDGET_MB"))
+            budget = (uint64_t)strtoull(e, nullptr, 10) << 20;
+          for (int k = 0; k < K; k++) {
+            const DevRegion::ColPlane *p = dev_colplane_get(
+                dev, pl.group_keys[k].col_id, budget, eng->stream,
+                &eng->plane_builds);
+            if (p && !p->n_rowparse && !p->n_dec)
+              kp[k] = PlaneRef{p->val, p->st, nullptr, 0};
+          }
+        }
+        if (planes_on && hash_plane_plan_ok(pl.sp)) {
+          psets.resize(1);
+          if (!plane_wire(eng, dev, pl.sp, &psets[0], true, nullptr,
+                          /*wire_group=*/false))
+            psets.clear();
+        }
+        uint32_t gk_slots = 1u << 16;
+        if (const char *e = getenv("COPR_GK_SLOTS")) {
+          unsigned long long v = strtoull(e, nullptr, 10);
+          if (v && v <= (1ull << 31) && !(v & (v - 1))) gk_slots = (uint32_t)v;
+        }
+        hipEventRecord(ev_a, eng->stream);
+        int grc = dev_group_ids(dev, pl.group_keys.data(), K, kp, gk_slots,
+                                eng->stream, &gm);
+        eng->group_dict_grows += gm.grows;
+        eng->group_row_source_runs += gm.row_source_runs;
+        if (grc == -3)
+          return SET_ERR(COPR_ERR_STORAGE, "row parse error on device");
+        if (grc == -2) return SET_ERR(COPR_ERR_OOM, "group id alloc");
+        if (grc) return SET_ERR(COPR_ERR_INTERNAL, "group id stage failed");
+        eng->group_multi_runs++;
+        eng->group_last_groups = gm.n_groups;
+        if (!psets.empty())
+          psets[0].g = PlaneRef{gm.gid_val, gm.gid_st, nullptr, 0};
+        else
+          gm_sorted = true;
+      }
+      if (gm_sorted) {
+        copr_region *r = regions[0];
+        ScanPlan sp = pl.sp;
+        sp.mode = 3;
+        wire_celldir(&sp, r->dev);
+        pick_tiling(r->dev, &sp, /*force_nopipe=*/true);
+        std::vector<SimpleAggAcc> h_accs;
+        std::vector<long long> h_gk;
+        std::vector<uint8_t> h_gs;
+        int n_seg = dev_int_sorted_agg(sp, r->dev, eng->stream, &h_accs, &h_gk,
+                                       &h_gs, gm.gid_val);
+        hipEventRecord(ev_b, eng->stream);
+        timed = true;
+        if (n_seg == -3)
+          return SET_ERR(COPR_ERR_STORAGE, "row parse error on device");
+        if (n_seg == -2) return SET_ERR(COPR_ERR_OOM, "sorted agg temp alloc");
+        if (n_seg < 0) return SET_ERR(COPR_ERR_INTERNAL, "sorted agg failed");
+        copr_status est = emit_multi(h_gk.data(), (uint64_t)n_seg,
+                                     h_accs.data(), nullptr);
+        if (est != COPR_OK) return est;
+      } else
       for (int attempt = 0; attempt < 4; attempt++) {
         /* the table buffers persist on the engine across requests: the
            per-request hipMalloc/hipFree set measured ~3 ms at cfg3 scale */
@@ -2718,7 +2931,8 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
           if (e == hipSuccess) e = hipMemsetAsync(ht.n_groups, 0, 8, eng->stream);
           if (e != hipSuccess) { free_ht(); return SET_ERR(COPR_ERR_INTERNAL, "ht init"); }
         }
-        hipEventRecord(ev_a, eng->stream);
+        /* several keys: ev_a went before stage 1 */
+        if (!pl.group_multi) hipEventRecord(ev_a, eng->stream);
         for (uint32_t rg = 0; rg < n_regions; rg++) {
           ScanPlan sp = pl.sp;
           sp.table_size = tsize;
@@ -2805,6 +3019,14 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         if (ng == -2) return SET_ERR(COPR_ERR_OOM, "table compact alloc");
         if (ng < 0 || ce != hipSuccess)
           return SET_ERR(COPR_ERR_INTERNAL, "table compact failed");
+        if (pl.group_multi) {
+          /* a group id is never INT64_MIN or NULL: reserved[] stays empty */
+          copr_status est =
+              emit_multi(h_keys.data(), h_keys.size(), h_accs.data(),
+                         any_dec ? h_ext.data() : nullptr);
+          if (est != COPR_OK) return est;
+          break;
+        }
         /* encode rows: occupied slots + reserved groups */
         size_t n_out_cols = pl.out_schema.size();
         bool enc_err = false;

@@ -4,12 +4,14 @@
 
 #include <stdint.h>
 #include <stddef.h>
+#include <string.h>
 #include <string>
 #include <vector>
 
 #include "../../include/copr_types.h"   /* scalar sig / tp enums */
 #include "plane_fold.h"                  /* CMP_*, Plane/Narrow/SplitFcArgs */
 #include "topn_keys.h"                   /* TopnKey, order-key transform, cut */
+#include "group_keys.h"                  /* GroupKey, tuple dictionary rules */
 
 namespace copr {
 
@@ -412,6 +414,52 @@ int dev_topn_keys_launch(const DevRegion &rgn, const uint32_t *d_rows,
                          uint64_t cnt, const TopnKey &key,
                          unsigned long long *d_u, uint8_t *d_rank,
                          unsigned int *d_err, void *stream);
+/* multi-key hash aggregation, stage 1 (group_multi.hip).
+ * One key's source: kind 0 = the column's plane (val / st), kind 1 = the
+ * row-bytes source, dev_topn_keys_launch's ascending (u, rank) pair per row
+ * (val = u, st = rank), decoded with topn_key_decode. */
+struct GkSrc {
+  const int64_t *val;
+  const uint8_t *st;
+  int32_t kind;
+  int32_t uns;
+  int32_t missing_null;          /* plane source: what PST_ABSENT stands for */
+  int32_t pad_;
+  int64_t missing_val;
+};
+struct GkArgs {
+  GkSrc k[COPR_GROUP_MAX_KEYS];
+  int32_t n_keys;
+};
+/* what stage 1 leaves on the device for stage 2 and the final gather */
+struct GroupIds {
+  int64_t *gid_val = nullptr;      /* [n_rows] (+ tail slack): the slot index */
+  uint8_t *gid_st = nullptr;       /* [n_rows] (+ tail slack), all PST_INT */
+  unsigned long long *slots = nullptr;   /* the dictionary */
+  uint32_t n_slots = 0;
+  unsigned int *d_flags = nullptr; /* [0] full, [1] fallback, [2..3] filled */
+  unsigned long long *row_u[COPR_GROUP_MAX_KEYS] = {};
+  uint8_t *row_rank[COPR_GROUP_MAX_KEYS] = {};
+  GkArgs args{};
+  uint64_t n_rows = 0;
+  uint64_t n_groups = 0;           /* filled slots */
+  uint32_t grows = 0;              /* dictionary doublings */
+  uint32_t row_source_runs = 0;    /* runs that read a key from the row bytes */
+};
+/* gid for every row of the region. keys[0..n_keys) are distinct int columns,
+ * planes[k].val non-null = key k reads that plane (every row INT, NULL or
+ * ABSENT, else the whole stage reruns on the row bytes). init_slots: a power
+ * of two. 0 ok, -1 internal, -2 oom, -3 row parse error; on failure g is
+ * freed. */
+int dev_group_ids(const DevRegion &rgn, const GroupKey *keys, int n_keys,
+                  const PlaneRef *planes, uint32_t init_slots, void *stream,
+                  GroupIds *g);
+/* the key cells of cnt groups named by slot index: (*vals)[k * cnt + i],
+ * (*nulls)[k * cnt + i] */
+int dev_group_gather(const GroupIds &g, const uint32_t *h_slots, uint64_t cnt,
+                     void *stream, std::vector<int64_t> *vals,
+                     std::vector<uint8_t> *nulls);
+void dev_group_free(GroupIds *g);
 /* fill keys[] with the EMPTY sentinel (INT64_MIN) */
 void dev_fill_keys(long long *keys, uint64_t n, void *stream);
 int dev_ht_compact(const HashAggTable &ht, uint32_t tsize, int n_aggs,
@@ -421,7 +469,8 @@ int dev_ht_compact(const HashAggTable &ht, uint32_t tsize, int n_aggs,
 int dev_int_sorted_agg(const ScanPlan &plan, const DevRegion &rgn,
                        void *stream, std::vector<SimpleAggAcc> *h_accs,
                        std::vector<long long> *h_gk,
-                       std::vector<uint8_t> *h_gs);
+                       std::vector<uint8_t> *h_gs,
+                       const int64_t *d_gid = nullptr);
 int dev_bytes_agg(const ScanPlan &plan, const DevRegion &rgn, void *stream,
                   std::vector<SimpleAggAcc> *h_accs,
                   std::vector<uint64_t> *h_kofs, std::vector<uint32_t> *h_klen,
@@ -486,6 +535,12 @@ struct copr_engine {
   uint64_t topn_multi_runs = 0;
   uint64_t topn_last_kept = 0;
   uint64_t topn_last_candidates = 0;
+  /* copr_engine_group_multi_runs / _last_groups / _dict_grows /
+     _row_source_runs */
+  uint64_t group_multi_runs = 0;
+  uint64_t group_last_groups = 0;
+  uint64_t group_dict_grows = 0;
+  uint64_t group_row_source_runs = 0;
   /* RCCL communicator state (copr_comm.cpp); null until copr_comm_create */
   void *comm_state = nullptr;
   /* hash-agg table cache: the per-request hipMalloc/hipFree set measured

@@ -5246,10 +5246,21 @@ int dev_blocks_build(const uint8_t *h_blocks, const uint64_t *h_block_offs,
  * compare (no fingerprint verify). Used when a FastHash request carries
  * FIRST, which the atomic-table path cannot order. Returns like
  * dev_stream_agg; group keys come back in h_gk. */
+/* multi-key grouping: the group id stands in for the key the
+   extract pass parsed; a kept row always has one */
+__global__ static void k_gid_keys(const int64_t *__restrict__ gid,
+                                  int64_t *__restrict__ gkey,
+                                  uint8_t *__restrict__ st, uint64_t n) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  gkey[i] = gid[i];
+  st[i] = st[i] ? 2 : 0;
+}
+
 int dev_int_sorted_agg(const ScanPlan &plan, const DevRegion &rgn,
                        void *stream, std::vector<SimpleAggAcc> *h_accs,
                        std::vector<long long> *h_gk,
-                       std::vector<uint8_t> *h_gs) {
+                       std::vector<uint8_t> *h_gs, const int64_t *d_gid) {
   hipStream_t s = (hipStream_t)stream;
   uint64_t n = rgn.n_kv;
   if (!n) return 0;
@@ -5281,6 +5292,9 @@ int dev_int_sorted_agg(const ScanPlan &plan, const DevRegion &rgn,
   if (e != hipSuccess) { freeall(); return -2; }
   ExtractOut eo{st, gkey, av, as_, nullptr, nullptr, nullptr};
   if (extract_launch(plan, rgn, eo, d_err, s)) { freeall(); return -1; }
+  if (d_gid)
+    hipLaunchKernelGGL(k_gid_keys, dim3((uint32_t)((n + 255) / 256)),
+                       dim3(256), 0, s, d_gid, gkey, st, n);
   unsigned int h_err = 0;
   e = hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);

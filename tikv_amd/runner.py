@@ -141,13 +141,16 @@ class DagSelect:
         ex.aggs = arr
         ex.n_aggs = len(aggs)
         if group_by is not None:
-            ge, keep = group_by.build()
-            self._keep += keep
-            garr = (F.CoprExpr * 1)(ge)
+            keys = group_by if isinstance(group_by, (list, tuple)) else [group_by]
+            garr = (F.CoprExpr * len(keys))()
+            for i, g in enumerate(keys):
+                ge, keep = g.build()
+                self._keep += keep
+                garr[i] = ge
             self._keep.append(garr)
             ex.group_by = garr
-            ex.n_group_by = 1
-            out_cols += 1
+            ex.n_group_by = len(keys)
+            out_cols += len(keys)
             self._has_group = True
         self.executors.append(ex)
         self._agg_out_cols = out_cols
@@ -158,7 +161,15 @@ class DagSelect:
         return self._agg(F.EXEC_SIMPLE_AGG, aggs)
 
     def hash_agg(self, aggs, group_by):
+        """group_by: one Expr, or a list of two to four column Exprs
+        (GROUP BY a, b ...). The response carries the
+        aggregate columns, then the group columns in list order."""
         return self._agg(F.EXEC_FAST_HASH_AGG, aggs, group_by)
+
+    def slow_hash_agg(self, aggs, group_by):
+        """BatchSlowHashAggregationExecutor, the kind TiDB sends for several
+        group-by expressions; with one it plans as hash_agg does."""
+        return self._agg(F.EXEC_SLOW_HASH_AGG, aggs, group_by)
 
     def stream_agg(self, aggs, group_by):
         """BatchStreamAggregationExecutor: groups are contiguous runs of
@@ -572,6 +583,17 @@ class Engine:
         return (self._lib.copr_engine_topn_multi_runs(self._h),
                 self._lib.copr_engine_topn_last_kept(self._h),
                 self._lib.copr_engine_topn_last_candidates(self._h))
+
+    def group_stats(self):
+        """(runs, last_groups, dict_grows, row_source_runs): requests served
+        by the multi-key group-by path since the engine was created, the
+        filled dictionary slots of the last of them, dictionary doublings,
+        and stage-1 runs that read a key from the row bytes. Requests with
+        one group-by expression move none of the four."""
+        return (self._lib.copr_engine_group_multi_runs(self._h),
+                self._lib.copr_engine_group_last_groups(self._h),
+                self._lib.copr_engine_group_dict_grows(self._h),
+                self._lib.copr_engine_group_row_source_runs(self._h))
 
     def close(self):
         if self._h:
