@@ -91,7 +91,9 @@ enum CoprExprNodeKind {
 /* Scalar function signatures (mirrors tipb::ScalarFuncSig variant names;
  * the subset map_expr_node_to_rpn_func supports natively here —
  * tidb_query_expr/src/lib.rs:435+. Int/Uint variants are selected by the
- * operands' UNSIGNED flags exactly as map_int_sig does (lib.rs:234). */
+ * operands' UNSIGNED flags exactly as map_int_sig does (lib.rs:234): the
+ * comparers and PLUS / MINUS / MULTIPLY all read them, and arithmetic with
+ * an unsigned operand yields BIGINT UNSIGNED or fails the request. */
 enum CoprScalarSig {
   COPR_SIG_LT_INT = 1, COPR_SIG_LE_INT, COPR_SIG_GT_INT, COPR_SIG_GE_INT,
   COPR_SIG_EQ_INT, COPR_SIG_NE_INT,

@@ -225,6 +225,42 @@ static int cmp_int(int64_t l, int64_t r, bool lu, bool ru) {
   return l < r ? -1 : l > r ? 1 : 0;
 }
 
+/* PLUS / MINUS / MULTIPLY, the IntInt / IntUint / UintInt / UintUint
+ * variants map_int_sig picks from the operands' UNSIGNED flags
+ * (impl_arithmetic.rs): with an unsigned operand the result is BIGINT
+ * UNSIGNED and must lie in [0, 2^64-1]. A negative signed factor times an
+ * unsigned one is out of range whatever the unsigned one is. False on
+ * overflow. */
+static bool arith_int(int sig, int64_t a, int64_t b, bool lu, bool ru,
+                      int64_t *res) {
+  if (!lu && !ru) {
+    if (sig == COPR_SIG_PLUS_INT) return !__builtin_add_overflow(a, b, res);
+    if (sig == COPR_SIG_MINUS_INT) return !__builtin_sub_overflow(a, b, res);
+    return !__builtin_mul_overflow(a, b, res);
+  }
+  uint64_t x = (uint64_t)a, y = (uint64_t)b, r = 0;
+  bool ovf;
+  if (sig == COPR_SIG_PLUS_INT) {
+    if (lu && ru) {
+      ovf = __builtin_add_overflow(x, y, &r);
+    } else {
+      int64_t s = lu ? b : a;          /* the signed operand */
+      uint64_t u = lu ? x : y;
+      ovf = s >= 0 ? __builtin_add_overflow(u, (uint64_t)s, &r)
+                   : __builtin_sub_overflow(u, 0 - (uint64_t)s, &r);
+    }
+  } else if (sig == COPR_SIG_MINUS_INT) {
+    if (lu && ru) ovf = __builtin_sub_overflow(x, y, &r);
+    else if (ru) ovf = a < 0 || __builtin_sub_overflow(x, y, &r);
+    else ovf = b >= 0 ? __builtin_sub_overflow(x, y, &r)
+                      : __builtin_add_overflow(x, 0 - y, &r);
+  } else {
+    ovf = (!lu && a < 0) || (!ru && b < 0) || __builtin_mul_overflow(x, y, &r);
+  }
+  *res = (int64_t)r;
+  return !ovf;
+}
+
 static bool eval_rpn(const CoprExpr &expr, Batch *batch,
                      const std::vector<CoprFieldType> &schema,
                      StackEntry *out) {
@@ -348,18 +384,18 @@ static bool eval_rpn(const CoprExpr &expr, Batch *batch,
               else out_e.vec.push_int(arg_i(0, li) == 0 ? 1 : 0);
             }
             break;
-          case COPR_SIG_PLUS_INT: case COPR_SIG_MINUS_INT: case COPR_SIG_MULTIPLY_INT:
+          case COPR_SIG_PLUS_INT: case COPR_SIG_MINUS_INT: case COPR_SIG_MULTIPLY_INT: {
+            bool lu = stack[base].ft_unsigned, ru = stack[base + 1].ft_unsigned;
             for (uint32_t li = 0; li < n_logical; li++) {
               if (arg_null(0, li) || arg_null(1, li)) { out_e.vec.push_null(); continue; }
-              int64_t a = arg_i(0, li), b = arg_i(1, li), res;
-              bool ovf;
-              if (node.sig == COPR_SIG_PLUS_INT) ovf = __builtin_add_overflow(a, b, &res);
-              else if (node.sig == COPR_SIG_MINUS_INT) ovf = __builtin_sub_overflow(a, b, &res);
-              else ovf = __builtin_mul_overflow(a, b, &res);
-              if (ovf) FAIL("BIGINT value is out of range");
+              int64_t res;
+              if (!arith_int(node.sig, arg_i(0, li), arg_i(1, li), lu, ru, &res))
+                FAIL(lu || ru ? "BIGINT UNSIGNED value is out of range"
+                              : "BIGINT value is out of range");
               out_e.vec.push_int(res);
             }
             break;
+          }
           case COPR_SIG_INT_IS_NULL:
             for (uint32_t li = 0; li < n_logical; li++)
               out_e.vec.push_int(arg_null(0, li) ? 1 : 0);

@@ -832,6 +832,9 @@ struct HostPlan {
   std::vector<copr::TopnKey> topn_keys;
   int dec2_col_offset = -1;
   int filter2_col_offset = -1;
+  /* offsets of the third and fourth column an RPN selection names (the
+     extra-capture channels), -1 = none */
+  int xcap_col_offset[2] = {-1, -1};
   uint64_t limit = UINT64_MAX;
 };
 
@@ -1173,10 +1176,11 @@ static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
 }
 
 
-/* general selection translation: flatten the (ANDed) condition programs
-   into a DevRpnNode program over <=2 distinct int columns. Falls back from
-   the fixed cmp fast path; mirrors the node set orc_exec eval_rpn accepts
-   for ints (expr_eval.rs:205,264). */
+/* general selection translation: flatten the condition programs into one
+   DevRpnNode program over <=4 distinct int columns, a gate node between
+   one condition and the next. Falls back from the fixed cmp fast path;
+   takes the node set orc_exec eval_rpn accepts for ints
+   (expr_eval.rs:205,264). */
 static copr_status translate_rpn(const CoprExecutor &ex, HostPlan *pl,
                                  ScanPlan *sp) {
   struct Slot { int64_t col_id; int off; };
@@ -1194,6 +1198,17 @@ static copr_status translate_rpn(const CoprExecutor &ex, HostPlan *pl,
   };
   for (uint32_t c = 0; c < ex.n_conditions; c++) {
     const CoprExpr &cond = ex.conditions[c];
+    if (c > 0) {
+      /* a later condition sees only the rows the earlier ones kept
+         (selection_executor.rs:86): the gate drops a row whose condition
+         value is not true and empties the stack for the next condition */
+      if (depth != 1) return COPR_ERR_INVALID_REQUEST;
+      if (n >= COPR_MAX_RPN) return COPR_ERR_UNSUPPORTED;
+      DevRpnNode gate{};
+      gate.kind = 4;
+      prog[n++] = gate;
+      depth = 0;
+    }
     for (uint32_t i = 0; i < cond.n_nodes; i++) {
       const CoprExprNode &en = cond.nodes[i];
       DevRpnNode nd{};
@@ -1256,13 +1271,6 @@ static copr_status translate_rpn(const CoprExecutor &ex, HostPlan *pl,
           return COPR_ERR_UNSUPPORTED;
       }
     }
-    if (c > 0) {
-      /* conditions AND together (selection_executor.rs:86) */
-      DevRpnNode nd{};
-      nd.kind = 3;
-      nd.sig = COPR_SIG_LOGICAL_AND;
-      if (!push(nd, -1)) return COPR_ERR_UNSUPPORTED;
-    }
   }
   if (depth != 1 || n == 0) return COPR_ERR_INVALID_REQUEST;
   /* capture channels + missing fill (scan default fill precedes the
@@ -1315,6 +1323,7 @@ static copr_status translate_rpn(const CoprExecutor &ex, HostPlan *pl,
     int idx = sp->n_aggs++;
     if (idx >= COPR_MAX_AGGS) return COPR_ERR_UNSUPPORTED;
     sp->aggs[idx] = ds;
+    pl->xcap_col_offset[k] = slots[2 + k].off;
     sp->xcap_idx[sp->n_xcap] = idx;
     copr_status st = fill(ci, &sp->xcap_missing_null[sp->n_xcap],
                           &sp->xcap_missing_val[sp->n_xcap]);
@@ -2421,11 +2430,20 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
       eng->dec2_col_off =
           (pl.sp.has_filter && pl.filter_col_offset >= 0 &&
            pl.filter_col_offset != pl.topn_off) ? pl.filter_col_offset : -1;
+      /* the selection decoded every column it names: those beyond the two
+         decode slots are decoded by the host assembly */
+      const int more[3] = {pl.sp.filter2_on && !pl.sp.filter2_is_real
+                               ? pl.filter2_col_offset : -1,
+                           pl.xcap_col_offset[0], pl.xcap_col_offset[1]};
+      for (int off : more)
+        if (off >= 0 && off != pl.topn_off && off != eng->dec2_col_off)
+          eng->host_dec_offs.push_back(off);
     }
     copr_status st2 = copr_dag_run(eng, &preq, &rp, 1, out);
     eng->dec_col_off = -1;
     eng->dec2_col_off = -1;
     eng->topn_dec.clear();
+    eng->host_dec_offs.clear();
     free_sub();
     if (st2 == COPR_OK && req->encode_type == 1) {
       std::vector<uint8_t> dat(out->data, out->data + out->data_len);
@@ -3362,6 +3380,35 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
           }
           unsigned long long cp = h_cells[i * pl.sp.n_out + off];
           uint32_t clen = (uint32_t)(cp & 0xFFFFFu);
+          const bool host_dec =
+              std::find(eng->host_dec_offs.begin(), eng->host_dec_offs.end(),
+                        (int)off) != eng->host_dec_offs.end();
+          if (host_dec && clen != 0xFFFFEu) {
+            /* an int column the original request's selection decoded: the
+               cell, or the default of an absent one, as a decoded datum. A v2
+               cell's re-encode below is that form already. */
+            const CoprColumnInfo &ci = pl.cols[off];
+            const uint8_t *dp = nullptr;
+            size_t dl = 0;
+            if (clen == 0xFFFFFu) {
+              dp = ci.default_val;
+              dl = dp ? ci.default_val_len : 0;
+            } else {
+              uint64_t rs = span_offs[i];
+              if (!(!idxp && span_offs[i + 1] - rs > 1 && vbase[rs] == 128)) {
+                dp = vbase + (cp >> 20);
+                dl = clen;
+              }
+            }
+            if (dp && dl) {
+              int64_t dv;
+              int dr = host_decode_int_datum(dp, dl, &dv);
+              if (dr < 0) return SET_ERR(COPR_ERR_STORAGE, "bad int cell");
+              if (dr == 1) resp.push_back(0);
+              else enc_datum_int(&resp, dv, (ci.ft.flag & COPR_FLAG_UNSIGNED) != 0);
+              continue;
+            }
+          }
           if (clen == 0xFFFFFu) {
             /* missing column: default value or NULL
                (table_scan_executor.rs:456-483) */

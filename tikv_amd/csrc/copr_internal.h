@@ -125,14 +125,18 @@ enum {
   DAGG_XCAP,
 };
 
-/* flattened RPN node for the device predicate evaluator (mirrors the
-   oracle's eval_rpn over RpnExpression — expr_eval.rs:205,264; int-typed
-   columns only; column refs resolve to capture slots 0/1 at plan time) */
+/* flattened RPN node for the device predicate evaluator (the node set of
+   the oracle's eval_rpn over RpnExpression — expr_eval.rs:205,264; int-typed
+   columns only; column refs resolve at plan time to capture slots 0..3: the
+   two filter channels, then the two extra-capture channels) */
 #define COPR_MAX_RPN 16
 struct DevRpnNode {
-  int32_t kind;   /* 0 col slot, 1 const int, 2 const NULL, 3 scalar func */
+  int32_t kind;   /* 0 col slot, 1 const int, 2 const NULL, 3 scalar func,
+                     4 gate: end of a condition that is not the last; drops
+                     the row unless the value on the stack is true */
   int32_t sig;    /* kind 3: CoprScalarSig */
-  int32_t slot;   /* kind 0: capture slot (0 = filter chan, 1 = filter2) */
+  int32_t slot;   /* kind 0: capture slot (0 = filter chan, 1 = filter2,
+                     2 / 3 = extra-capture channels) */
   int32_t uns;    /* value unsignedness (col ft / const kind / func out ft) */
   int64_t cval;   /* kind 1 */
 };
@@ -531,6 +535,10 @@ struct copr_engine {
     std::vector<uint8_t> nulls;
   };
   std::vector<DecOverride> topn_dec;
+  /* single-key TopN sub-region project: int columns the original request's
+     selection decoded beyond the two decode slots; the host assembly emits
+     them decoded from the cell bytes. Empty outside that call. */
+  std::vector<int> host_dec_offs;
   /* copr_engine_topn_multi_runs / _last_kept / _last_candidates */
   uint64_t topn_multi_runs = 0;
   uint64_t topn_last_kept = 0;

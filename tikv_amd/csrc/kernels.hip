@@ -940,9 +940,54 @@ __device__ static inline bool d_filter2_keep(const ScanPlan &plan,
                                    plan.filter2_const_unsigned));
 }
 
-/* evaluate the plan's RPN predicate over the two captured columns.
- * Mirrors orc_exec eval_rpn node-for-node (NULL-aware logical ops
- * impl_op.rs; signed overflow on int arithmetic errors the request).
+/* PLUS / MINUS / MULTIPLY in the IntInt / IntUint / UintInt / UintUint
+ * variant the operands' UNSIGNED flags select (impl_arithmetic.rs): with an
+ * unsigned operand the result is BIGINT UNSIGNED and must lie in
+ * [0, 2^64-1]; a negative signed factor times an unsigned one is out of
+ * range whatever the unsigned one is. Returns true on overflow. */
+__device__ static inline bool d_arith_int(int32_t sig, int64_t a, int64_t b,
+                                          bool lu, bool ru, int64_t *res) {
+  if (!lu && !ru) {
+    long long r;
+    bool ovf =
+        sig == COPR_SIG_PLUS_INT
+            ? __builtin_add_overflow((long long)a, (long long)b, &r)
+            : sig == COPR_SIG_MINUS_INT
+                  ? __builtin_sub_overflow((long long)a, (long long)b, &r)
+                  : __builtin_mul_overflow((long long)a, (long long)b, &r);
+    *res = r;
+    return ovf;
+  }
+  unsigned long long x = (unsigned long long)a, y = (unsigned long long)b, r;
+  bool ovf;
+  if (sig == COPR_SIG_PLUS_INT) {
+    if (lu && ru) {
+      ovf = __builtin_add_overflow(x, y, &r);
+    } else {
+      int64_t s = lu ? b : a;            /* the signed operand */
+      unsigned long long u = lu ? x : y;
+      ovf = s >= 0 ? __builtin_add_overflow(u, (unsigned long long)s, &r)
+                   : __builtin_sub_overflow(u, 0 - (unsigned long long)s, &r);
+    }
+  } else if (sig == COPR_SIG_MINUS_INT) {
+    if (lu && ru) ovf = __builtin_sub_overflow(x, y, &r);
+    else if (ru) ovf = __builtin_sub_overflow(x, y, &r) || a < 0;
+    else ovf = b >= 0 ? __builtin_sub_overflow(x, y, &r)
+                      : __builtin_add_overflow(x, 0 - y, &r);
+  } else {
+    ovf = __builtin_mul_overflow(x, y, &r) || (!lu && a < 0) || (!ru && b < 0);
+  }
+  *res = (int64_t)r;
+  return ovf;
+}
+
+/* evaluate the plan's RPN predicate over the captured columns: NULL-aware
+ * logical ops (impl_op.rs), comparers and arithmetic in the variant the
+ * operands' UNSIGNED flags select; overflow errors the request. A gate node
+ * (kind 4) ends every condition of the selection but the last: a row whose
+ * condition value is not true is dropped there and no later node sees it,
+ * as selection_executor.rs:86 hands a later condition only the rows the
+ * earlier ones kept.
  * Returns keep; *err set on overflow / malformed program. */
 __device__ static inline bool d_rpn_keep(const ScanPlan &plan,
                                          bool f1_found, bool f1_null,
@@ -987,6 +1032,10 @@ __device__ static inline bool d_rpn_keep(const ScanPlan &plan,
       if (sp >= 4) { *err = true; return false; }
       sv[sp] = 0; sn[sp] = 1; su[sp] = 0;
       sp++;
+    } else if (nd.kind == 4) {
+      if (sp != 1) { *err = true; return false; }
+      if (sn[0] != 0 || sv[0] == 0) return false;
+      sp = 0;
     } else {
       int na = (nd.sig == COPR_SIG_UNARY_NOT ||
                 nd.sig == COPR_SIG_INT_IS_NULL ||
@@ -1031,16 +1080,10 @@ __device__ static inline bool d_rpn_keep(const ScanPlan &plan,
         case COPR_SIG_PLUS_INT: case COPR_SIG_MINUS_INT:
         case COPR_SIG_MULTIPLY_INT: {
           if (n0 || n1) { rn = 1; break; }
-          bool ovf;
-          long long res;
-          if (nd.sig == COPR_SIG_PLUS_INT)
-            ovf = __builtin_add_overflow((long long)a0, (long long)a1, &res);
-          else if (nd.sig == COPR_SIG_MINUS_INT)
-            ovf = __builtin_sub_overflow((long long)a0, (long long)a1, &res);
-          else
-            ovf = __builtin_mul_overflow((long long)a0, (long long)a1, &res);
-          if (ovf) { *err = true; return false; }
-          rv = res;
+          if (d_arith_int(nd.sig, a0, a1, su[b] != 0, su[b + 1] != 0, &rv)) {
+            *err = true;
+            return false;
+          }
           break;
         }
         case COPR_SIG_INT_IS_NULL: rv = n0 ? 1 : 0; break;
@@ -4446,14 +4489,20 @@ int dev_topn_select(const ScanPlan &plan, const DevRegion &rgn,
   hipError_t e = hipSuccess;
   if (e == hipSuccess) e = hipMalloc(&st, n);
   if (e == hipSuccess) e = hipMalloc(&gkey, n * 8);
-  if (e == hipSuccess) e = hipMalloc(&cav, 16);   /* NAGGS=0 stubs */
-  if (e == hipSuccess) e = hipMalloc(&cas, 16);
+  /* no aggregates, but the predicate's capture-only slots sit at
+     aggs[0..n_xcap) and the extract pass collects exactly n_aggs columns
+     (one at least): with two of them n_aggs = 0 would leave the second
+     channel reading as 0. The pass writes one (unused) contribution cell per
+     slot and row. */
+  const uint64_t nx = plan.n_xcap > 0 ? (uint64_t)plan.n_xcap : 0;
+  if (e == hipSuccess) e = hipMalloc(&cav, nx ? nx * n * 8 : 16);
+  if (e == hipSuccess) e = hipMalloc(&cas, nx ? nx * n : 16);
   if (e == hipSuccess) e = hipMalloc(&d_err, 4);
   if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, 4, s);
   if (e != hipSuccess) { freeall(); return -2; }
   ExtractOut eo{st, gkey, (int64_t *)cav, cas, nullptr, nullptr, nullptr};
   ScanPlan p0 = plan;
-  p0.n_aggs = 0;
+  p0.n_aggs = (int32_t)nx;
   if (extract_launch(p0, rgn, eo, d_err, s)) { freeall(); return -1; }
   unsigned int h_err = 0;
   e = hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s);
