@@ -77,6 +77,8 @@ extern "C" void copr_engine_destroy(copr_engine *eng) {
   hipFree(eng->d_simple_ext);
   hipFree(eng->d_fcn_state);
   if (eng->h_fcn_out) hipHostFree(eng->h_fcn_out);
+  if (eng->ev_a) hipEventDestroy(eng->ev_a);
+  if (eng->ev_b) hipEventDestroy(eng->ev_b);
   if (eng->stream) hipStreamDestroy(eng->stream);
   delete eng;
 }
@@ -2294,15 +2296,22 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
      reported in summaries[0].time_processed_ns (the ExecSummary surface the
      reference fills per executor slot, execute_stats.rs:43-76). bench.py's
      roofline leg reads this. */
-  struct EventPair {             /* RAII: every error return destroys both */
-    hipEvent_t a = nullptr, b = nullptr;
-    EventPair() { hipEventCreate(&a); hipEventCreate(&b); }
-    ~EventPair() {
-      if (a) hipEventDestroy(a);
-      if (b) hipEventDestroy(b);
+  /* The pair belongs to the engine (created here on the first request,
+     destroyed in copr_engine_destroy), so no return below owns an event: none
+     can leak or free one twice. A pair that could not be created stays null
+     and the request runs untimed. */
+  if (!eng->ev_tried) {
+    eng->ev_tried = true;
+    if (hipEventCreate(&eng->ev_a) != hipSuccess) eng->ev_a = nullptr;
+    if (hipEventCreate(&eng->ev_b) != hipSuccess) eng->ev_b = nullptr;
+    if (!eng->ev_a || !eng->ev_b) {
+      (void)hipGetLastError();
+      if (eng->ev_a) hipEventDestroy(eng->ev_a);
+      if (eng->ev_b) hipEventDestroy(eng->ev_b);
+      eng->ev_a = eng->ev_b = nullptr;
     }
-  } ev;
-  hipEvent_t ev_a = ev.a, ev_b = ev.b;
+  }
+  hipEvent_t ev_a = eng->ev_a, ev_b = eng->ev_b;
   float kernel_ms = 0.0f;
   bool timed = false;
 

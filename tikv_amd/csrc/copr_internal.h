@@ -572,6 +572,13 @@ struct copr_engine {
   unsigned long long *d_fcn_state = nullptr;
   unsigned long long *h_fcn_out = nullptr;
   bool fcn_dirty = false;
+  /* the event pair copr_dag_run times its launches with: created on the
+     first request (ev_tried = that has happened, whatever came of it), kept
+     for every later one, destroyed with the engine. Null after a failed
+     creation: requests then run untimed. Created without a lock: like the
+     rest of copr_dag_run, the pair relies on one thread per engine. */
+  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  bool ev_tried = false;
   /* diagnostics (copr_engine_plane_launches / _builds /
      copr_engine_hash_plane_launches / _narrow_launches / _narrow_builds) */
   uint64_t plane_launches = 0;

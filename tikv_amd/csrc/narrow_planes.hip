@@ -239,6 +239,35 @@ fcn_block_count(unsigned long long cnt, unsigned long long *__restrict__ cnt_out
   }
 }
 
+/* The packed count of fold_packed_out (plane_fold.h, which mirrors this bit
+ * for bit) over the eight 16-bit rows of one 16 B vector, two rows per
+ * instruction and four instructions per word: subtract, subtract clamped at
+ * zero, min with one, add. The counts stay packed, one per half of acc, and
+ * packed_sum adds the halves; a half holds up to 0xFFFF, a lane's iteration
+ * adds at most 16. Inline assembly: the compiler unpacks the clamped subtract
+ * and the min when they are written with vector types. */
+__device__ __forceinline__ uint32_t
+packed_out_acc(uint4 v, uint32_t lo_pk, uint32_t span_pk, uint32_t acc) {
+  const uint32_t ones = 0x00010001u;
+  uint32_t t;
+  /* one statement for the vector: the compiler pads every asm statement
+     with an s_nop */
+#define COPR_PK_OUT(W)                                                       \
+  "v_pk_sub_u16 %0, " W ", %6\n\t"                                           \
+  "v_pk_sub_u16 %0, %0, %7 clamp\n\t"                                        \
+  "v_pk_min_u16 %0, %0, %8\n\t"                                              \
+  "v_pk_add_u16 %1, %1, %0\n\t"
+  asm(COPR_PK_OUT("%2") COPR_PK_OUT("%3") COPR_PK_OUT("%4") COPR_PK_OUT("%5")
+      : "=&v"(t), "+v"(acc)
+      : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w), "s"(lo_pk), "s"(span_pk),
+        "s"(ones));
+#undef COPR_PK_OUT
+  return acc;
+}
+__device__ __forceinline__ uint32_t packed_sum(uint32_t acc) {
+  return (acc & 0xFFFFu) + (acc >> 16);
+}
+
 /* Filter+count over a narrow plane of 1 or 2 bytes per row. Each lane loads
  * 16 B = 16 / sizeof(T) rows, UNR loads in flight, grid-stride; the row test
  * is the 32-bit form of k_plane_fc's (narrow_fc_fold, plane_fold.h). Every
@@ -258,9 +287,30 @@ k_plane_fcn(const uint4 *__restrict__ data, uint64_t n_rows, NarrowFcArgs nf,
   unsigned long long cnt = 0;
   const uint64_t n_vec = (n_rows + R - 1) / R;
   const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
-  for (uint64_t p0 = (uint64_t)blockIdx.x * 256u * UNR + threadIdx.x;
-       p0 < n_vec; p0 += step) {
+  /* the packed count's constants; a 2-byte plane's lo + span <= 0xFFFF, and
+     the "never" form's span saturates to every row */
+  const uint32_t lo_pk = fold_pack16(nf.lo), span_pk = fold_pack16(nf.span);
+  /* b0 = p0 - threadIdx.x, the block's first vector, kept beside p0 so that
+     the compiler sees it is the same in every lane */
+  uint64_t b0 = (uint64_t)blockIdx.x * 256u * UNR;
+  for (uint64_t p0 = b0 + threadIdx.x; p0 < n_vec; p0 += step, b0 += step) {
     uint4 v[UNR];
+    if constexpr (sizeof(T) == 2) {
+      /* every row of the block's iteration is inside the plane (uniform):
+         no clamp, no live mask, two rows per instruction */
+      if ((b0 + 256u * UNR) * R <= n_rows) {
+        #pragma unroll
+        for (int u = 0; u < UNR; u++) v[u] = data[p0 + (uint64_t)u * 256u];
+        __builtin_amdgcn_sched_barrier(0);
+        uint32_t acc = 0;
+        #pragma unroll
+        for (int u = 0; u < UNR; u++)
+          acc = packed_out_acc(v[u], lo_pk, span_pk, acc);
+        const uint32_t out = packed_sum(acc);
+        cnt += inv ? out : UNR * R - out;
+        continue;
+      }
+    }
     #pragma unroll
     for (int u = 0; u < UNR; u++) {
       uint64_t p = min(p0 + (uint64_t)u * 256u, n_vec - 1);
@@ -302,7 +352,11 @@ k_plane_fcn(const uint4 *__restrict__ data, uint64_t n_rows, NarrowFcArgs nf,
  * the first is used, and puts the flagged rows through the full test. Rows at
  * or beyond n_rows are never flagged: the tail slack holds arbitrary bytes.
  * With every row flagged the low loads are as coalesced as the high ones and
- * the launch reads n_rows x 4 bytes, as k_plane_fcn<uint32_t> did. */
+ * the launch reads n_rows x 4 bytes, as k_plane_fcn<uint32_t> did.
+ * An iteration whose every row is inside the plane first counts its rows
+ * packed and classifies them one by one only in a wave that
+ * holds an open row; the iteration with the plane's last vector classifies
+ * every row under its live mask. */
 __global__ void __launch_bounds__(256)
 k_plane_fcs(const uint4 *__restrict__ hi, const uint4 *__restrict__ lo,
             uint64_t n_rows, SplitFcArgs sf,
@@ -315,37 +369,77 @@ k_plane_fcs(const uint4 *__restrict__ hi, const uint4 *__restrict__ lo,
   unsigned long long cnt = 0;
   const uint64_t n_vec = (n_rows + R - 1) / R;
   const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
-  for (uint64_t p0 = (uint64_t)blockIdx.x * 256u * UNR + threadIdx.x;
-       p0 < n_vec; p0 += step) {
+  /* b0 = p0 - threadIdx.x, the block's first vector, kept beside p0 so that
+     the compiler sees it is the same in every lane */
+  uint64_t b0 = (uint64_t)blockIdx.x * 256u * UNR;
+  for (uint64_t p0 = b0 + threadIdx.x; p0 < n_vec; p0 += step, b0 += step) {
     uint4 v[UNR];
-    #pragma unroll
-    for (int u = 0; u < UNR; u++) {
-      uint64_t p = min(p0 + (uint64_t)u * 256u, n_vec - 1);
-      v[u] = hi[p];
-    }
-    /* all four loads issue before the first is used */
-    __builtin_amdgcn_sched_barrier(0);
-    /* one bit per row, vector u in bits 8u .. 8u + 7 */
-    uint32_t livem = 0, maybe = 0, sure = 0;
-    #pragma unroll
-    for (int u = 0; u < UNR; u++) {
-      const uint64_t p = p0 + (uint64_t)u * 256u;
-      uint32_t live = 0;
-      if (p < n_vec) {
-        const uint64_t left = n_rows - p * R;
-        live = left < R ? (uint32_t)left : R;
-      }
-      livem |= ((1u << live) - 1u) << (u * R);
-      const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+    /* one bit per row, vector u in bits 8u .. 8u + 7: the rows inside the
+       plane and the open rows; in = the rows phase one decided in */
+    uint32_t livem = ~0u, in = 0, amb = 0;
+    bool classify = true;
+    if ((b0 + 256u * UNR) * R <= n_rows) {
+      /* Fast path: every row of the block's iteration is inside
+         the plane, so there is no clamp and no live mask, and the rows are
+         counted two per instruction, never unpacked: out_maybe and out_sure
+         rows outside the two intervals. sure lies inside maybe, so the lane
+         holds an open row exactly when the counts differ; only a wave with
+         such a lane classifies its rows one by one, from the same registers. */
       #pragma unroll
-      for (uint32_t j = 0; j < R; j++) {
-        const uint32_t h = (j & 1u) ? w[j / 2] >> 16 : w[j / 2] & 0xFFFFu;
-        maybe |= (split_maybe(h, sf) ? 1u : 0u) << (u * R + j);
-        sure |= (split_sure(h, sf) ? 1u : 0u) << (u * R + j);
+      for (int u = 0; u < UNR; u++) v[u] = hi[p0 + (uint64_t)u * 256u];
+      /* all four loads issue before the first is used */
+      __builtin_amdgcn_sched_barrier(0);
+      uint32_t acc_m = 0;
+      #pragma unroll
+      for (int u = 0; u < UNR; u++)
+        acc_m = packed_out_acc(v[u], sf.maybe_lo_pk, sf.maybe_span_pk, acc_m);
+      const uint32_t out_maybe = packed_sum(acc_m);
+      /* an empty sure interval has no 16-bit form: every row is outside it */
+      uint32_t out_sure = UNR * R;
+      if (!sf.sure_empty) {
+        uint32_t acc_s = 0;
+        #pragma unroll
+        for (int u = 0; u < UNR; u++)
+          acc_s = packed_out_acc(v[u], sf.sure_lo_pk, sf.sure_span_pk, acc_s);
+        out_sure = packed_sum(acc_s);
+      }
+      in = UNR * R - out_sure;
+      classify = __builtin_amdgcn_ballot_w64(out_sure != out_maybe) != 0;
+    } else {
+      #pragma unroll
+      for (int u = 0; u < UNR; u++) {
+        uint64_t p = min(p0 + (uint64_t)u * 256u, n_vec - 1);
+        v[u] = hi[p];
+      }
+      /* all four loads issue before the first is used */
+      __builtin_amdgcn_sched_barrier(0);
+      livem = 0;
+      #pragma unroll
+      for (int u = 0; u < UNR; u++) {
+        const uint64_t p = p0 + (uint64_t)u * 256u;
+        uint32_t live = 0;
+        if (p < n_vec) {
+          const uint64_t left = n_rows - p * R;
+          live = left < R ? (uint32_t)left : R;
+        }
+        livem |= ((1u << live) - 1u) << (u * R);
       }
     }
-    uint32_t in = __popc(sure & livem);
-    const uint32_t amb = maybe & ~sure & livem;
+    if (classify) {             /* wave-uniform */
+      uint32_t maybe = 0, sure = 0;
+      #pragma unroll
+      for (int u = 0; u < UNR; u++) {
+        const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+        #pragma unroll
+        for (uint32_t j = 0; j < R; j++) {
+          const uint32_t h = (j & 1u) ? w[j / 2] >> 16 : w[j / 2] & 0xFFFFu;
+          maybe |= (split_maybe(h, sf) ? 1u : 0u) << (u * R + j);
+          sure |= (split_sure(h, sf) ? 1u : 0u) << (u * R + j);
+        }
+      }
+      in = __popc(sure & livem);
+      amb = maybe & ~sure & livem;
+    }
     const unsigned long long open_lanes =
         __builtin_amdgcn_ballot_w64(amb != 0);
     if (open_lanes != 0) {
@@ -397,10 +491,14 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
   /* a split plane streams its 2-byte high halves */
   const uint32_t rows_per_vec = p.nar_lo_off ? 8u : 16u / p.nar_w;
   const uint64_t n_vec = (n_rows + rows_per_vec - 1) / rows_per_vec;
-  /* 2048 blocks = 8 per CU, each lane with 4 x 16 B in flight; a finalizing
-     launch needs at least one block even over no rows */
+  /* 2048 blocks = 8 per CU, each lane with 4 x 16 B in flight. k_plane_fcs,
+     whose packed count leaves a wave little to do per byte, measured fastest
+     at 768 = 3 per CU on the one shape tried: the benchmark's column at 100 M
+     and 150 M rows, plain and with every row through both halves (DESIGN
+     §9l). It is a tuned figure, not a rule; COPR_NARROW_GRID overrides it. A
+     finalizing launch needs at least one block even over no rows */
   uint64_t nb = (n_vec + 256u * 4 - 1) / (256u * 4);
-  const uint64_t cap = grid_cap ? grid_cap : 2048u;
+  const uint64_t cap = grid_cap ? grid_cap : p.nar_lo_off ? 768u : 2048u;
   if (nb > cap) nb = cap;
   if (!nb) nb = 1;
   const uint4 *data = (const uint4 *)p.nar;

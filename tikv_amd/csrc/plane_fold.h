@@ -89,12 +89,29 @@ inline bool narrow_fc_fold(const PlaneFcArgs &fa, int64_t base, uint64_t nmax,
      sure  = maybe shrunk to the h whose every l passes the test;
    only a row in maybe and not in sure needs its l. Both are range tests in
    32-bit unsigned arithmetic, (h - x_lo) <= x_span; an empty sure interval is
-   {0x10000, 0}, false for every h <= 0xFFFF. */
+   {0x10000, 0}, false for every h <= 0xFFFF.
+   The *_pk fields are the same intervals for the packed count,
+   the 16-bit value in both halves of a word. The empty sure interval has no
+   16-bit form: sure_empty says so and sure_*_pk are then unused (zero). */
 struct SplitFcArgs {
   uint32_t lo, span, invert;       /* the full test, as NarrowFcArgs */
   uint32_t maybe_lo, maybe_span;
   uint32_t sure_lo, sure_span;
+  uint32_t maybe_lo_pk, maybe_span_pk;
+  uint32_t sure_lo_pk, sure_span_pk;
+  uint32_t sure_empty;
 };
+
+#if defined(__HIP__) || defined(__HIPCC__)
+#define COPR_FOLD_HD __attribute__((host)) __attribute__((device))
+#else
+#define COPR_FOLD_HD
+#endif
+
+/* x (<= 0xFFFF, larger values saturate) in both 16-bit halves of a word */
+COPR_FOLD_HD inline uint32_t fold_pack16(uint32_t x) {
+  return (x > 0xFFFFu ? 0xFFFFu : x) * 0x10001u;
+}
 
 /* NarrowFcArgs -> SplitFcArgs. [lo, lo + span] does not wrap (narrow_fc_fold
    guarantees it), so its "never" form, the whole range inverted, comes out as
@@ -121,13 +138,48 @@ inline void split_fc_fold(const NarrowFcArgs &nf, bool all_lo,
     sf->sure_lo = (uint32_t)s_lo;
     sf->sure_span = (uint32_t)(s_hi - s_lo);
   }
+  sf->maybe_lo_pk = fold_pack16(sf->maybe_lo);
+  sf->maybe_span_pk = fold_pack16(sf->maybe_span);
+  sf->sure_empty = sf->sure_lo > 0xFFFFu ? 1u : 0u;
+  sf->sure_lo_pk = sf->sure_empty ? 0u : fold_pack16(sf->sure_lo);
+  sf->sure_span_pk = sf->sure_empty ? 0u : fold_pack16(sf->sure_span);
 }
 
-#if defined(__HIP__) || defined(__HIPCC__)
-#define COPR_FOLD_HD __attribute__((host)) __attribute__((device))
-#else
-#define COPR_FOLD_HD
-#endif
+/* The packed count: how many of the two 16-bit halves of w lie
+   outside [lo, lo + span], lo and span the same 16-bit value in both halves
+   of lo_pk and span_pk and lo + span <= 0xFFFF. Four steps, each one packed
+   16-bit instruction on the device (narrow_planes.hip, packed_out_acc):
+     d = w - lo        per half, wrapping      (a half below lo wraps high)
+     e = d - span      per half, clamped at 0  (0 exactly when d <= span)
+     m = min(e, 1)     per half
+     count = m.lo + m.hi
+   This is the arithmetic the device code is meant to perform, one word at a
+   time and summed at once; the device helper takes a 16 B vector, keeps the
+   two counts packed in its accumulator and sums the halves once per
+   iteration (packed_sum). The CPU test checks this arithmetic against the
+   per-row tests. That the inline assembly performs it (clamp semantics,
+   operand order) is checked by the GPU tests alone (test_packed_fc.py). */
+COPR_FOLD_HD inline uint32_t fold_pk_sub_u16(uint32_t a, uint32_t b) {
+  return ((a - (b & 0xFFFFu)) & 0xFFFFu) |
+         ((a - (b & 0xFFFF0000u)) & 0xFFFF0000u);
+}
+COPR_FOLD_HD inline uint32_t fold_pk_sub_sat_u16(uint32_t a, uint32_t b) {
+  const uint32_t al = a & 0xFFFFu, bl = b & 0xFFFFu;
+  const uint32_t ah = a >> 16, bh = b >> 16;
+  return (al > bl ? al - bl : 0u) | ((ah > bh ? ah - bh : 0u) << 16);
+}
+COPR_FOLD_HD inline uint32_t fold_pk_min_u16(uint32_t a, uint32_t b) {
+  const uint32_t al = a & 0xFFFFu, bl = b & 0xFFFFu;
+  const uint32_t ah = a >> 16, bh = b >> 16;
+  return (al < bl ? al : bl) | ((ah < bh ? ah : bh) << 16);
+}
+COPR_FOLD_HD inline uint32_t fold_packed_out(uint32_t w, uint32_t lo_pk,
+                                             uint32_t span_pk) {
+  const uint32_t d = fold_pk_sub_u16(w, lo_pk);
+  const uint32_t e = fold_pk_sub_sat_u16(d, span_pk);
+  const uint32_t m = fold_pk_min_u16(e, 0x00010001u);
+  return (m & 0xFFFFu) + (m >> 16);
+}
 
 /* the row rule of a split plane, before invert: keep = in != invert.
    k_plane_fcs applies the three steps in two phases, the first two to every
