@@ -129,6 +129,10 @@ uint64_t    copr_engine_group_multi_runs(const copr_engine *);
 uint64_t    copr_engine_group_last_groups(const copr_engine *);
 uint64_t    copr_engine_group_dict_grows(const copr_engine *);
 uint64_t    copr_engine_group_row_source_runs(const copr_engine *);
+/* Chunked (encode_type = 1) project responses built on the device, by the
+ * fixed-8 encoder or by the bytes/decimal one; monotonic. A
+ * request that fell back to the host re-encode does not move it. */
+uint64_t    copr_engine_dev_chunk_runs(const copr_engine *);
 
 /* ---- checksum (REQ_TYPE_CHECKSUM = 105; src/coprocessor/checksum.rs:59-114) ----
  * CRC-64/XZ per KV over key||value, XOR-folded (order-independent). */

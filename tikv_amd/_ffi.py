@@ -179,7 +179,8 @@ def load_lib():
     for name in ("copr_engine_group_multi_runs",
                  "copr_engine_group_last_groups",
                  "copr_engine_group_dict_grows",
-                 "copr_engine_group_row_source_runs"):
+                 "copr_engine_group_row_source_runs",
+                 "copr_engine_dev_chunk_runs"):
         getattr(lib, name).restype = C.c_uint64
         getattr(lib, name).argtypes = [C.c_void_p]
     lib.copr_checksum.restype = C.c_int

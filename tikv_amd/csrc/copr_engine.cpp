@@ -135,6 +135,10 @@ extern "C" uint64_t copr_engine_topn_last_candidates(const copr_engine *eng) {
   return eng ? eng->topn_last_candidates : 0;
 }
 
+extern "C" uint64_t copr_engine_dev_chunk_runs(const copr_engine *eng) {
+  return eng ? eng->dev_chunk_runs : 0;
+}
+
 /* ---------------- region ---------------- */
 extern "C" copr_status copr_region_create(copr_engine *eng,
                                           const uint8_t *keys, const uint64_t *key_offs,
@@ -2122,6 +2126,20 @@ static bool e_var_u64(const uint8_t *p, size_t rem, uint64_t *v, size_t *n) {
   return false;
 }
 
+/* a decimal's 40-byte chunk form (decimal.rs:2135-2142) */
+static void e_dec_chunk_struct(const prod::PDec &d, uint8_t rf,
+                               uint8_t buf[40]) {
+  buf[0] = d.int_cnt; buf[1] = d.frac_cnt; buf[2] = rf;
+  buf[3] = d.negative ? 1 : 0;
+  for (int i = 0; i < 9; i++) {
+    uint32_t w = d.word_buf[i];
+    buf[4 + 4 * i] = (uint8_t)w;
+    buf[5 + 4 * i] = (uint8_t)(w >> 8);
+    buf[6 + 4 * i] = (uint8_t)(w >> 16);
+    buf[7 + 4 * i] = (uint8_t)(w >> 24);
+  }
+}
+
 static size_t e_chunk_append_datum(EChunkCol *c, const uint8_t *p,
                                    size_t rem) {
   if (!rem) return 0;
@@ -2169,15 +2187,7 @@ static size_t e_chunk_append_datum(EChunkCol *c, const uint8_t *p,
       size_t used = 0;
       if (!prod::pdec_decode(p + 1, rem - 1, &d, &rf, &used)) return 0;
       uint8_t buf[40];
-      buf[0] = d.int_cnt; buf[1] = d.frac_cnt; buf[2] = rf;
-      buf[3] = d.negative ? 1 : 0;
-      for (int i = 0; i < 9; i++) {
-        uint32_t w = d.word_buf[i];
-        buf[4 + 4 * i] = (uint8_t)w;
-        buf[5 + 4 * i] = (uint8_t)(w >> 8);
-        buf[6 + 4 * i] = (uint8_t)(w >> 16);
-        buf[7 + 4 * i] = (uint8_t)(w >> 24);
-      }
+      e_dec_chunk_struct(d, rf, buf);
       c->app_fixed(buf, 40);
       return 1 + used;
     }
@@ -2190,8 +2200,28 @@ static size_t e_chunk_append_datum(EChunkCol *c, const uint8_t *p,
       c->app_var(p + 1 + nb, (size_t)n);
       return 1 + nb + (size_t)n;
     }
+    case 1: {
+      /* memcomparable bytes (what an index key carries): groups of 8 data
+         bytes + a marker; 0xFF = full group, else 0xFF - marker zero pads */
+      std::vector<uint8_t> raw;
+      size_t pos = 1;
+      for (;;) {
+        if (pos + 9 > rem) return 0;
+        const uint8_t *g = p + pos;
+        pos += 9;
+        if (g[8] == 0xFF) { raw.insert(raw.end(), g, g + 8); continue; }
+        size_t pad = 0xFFu - g[8];
+        if (pad > 8) return 0;
+        for (size_t i = 8 - pad; i < 8; i++)
+          if (g[i]) return 0;
+        raw.insert(raw.end(), g, g + 8 - pad);
+        break;
+      }
+      c->app_var(raw.data(), raw.size());
+      return pos;
+    }
     default:
-      return 0;   /* memcomparable bytes not produced by these paths */
+      return 0;
   }
 }
 
@@ -3118,7 +3148,8 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
 
       /* ---- device TypeChunk fast path (kernels.hip dev_chunk_encode):
          single region, table or index project, every output column
-         chunk-encodes as an 8-byte fixed value. Skips the span-stream +
+         chunk-encodes as an 8-byte fixed value, or (chunk_var.hip
+         dev_chunk_encode_var) as bytes or a decimal. Skips the span-stream +
          cell-directory D2H and the serial host datum->chunk re-encode.
          Any row the device cannot encode falls back to the host path
          below (bit-identical either way — tests compare both). */
@@ -3126,6 +3157,14 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         const char *dc_env = getenv("COPR_DEV_CHUNK");
         bool dc_on = !(dc_env && dc_env[0] == '0');
         std::vector<copr::ChunkColSpec> specs(req->n_output_offsets);
+        /* bytes / decimal columns: ctype per column and the
+           chunk form of their defaults; any such column routes the request
+           to dev_chunk_encode_var */
+        std::vector<int32_t> ctypes(req->n_output_offsets, 0);
+        std::vector<uint32_t> def_off(req->n_output_offsets, 0);
+        std::vector<uint32_t> def_len(req->n_output_offsets, 0);
+        std::vector<uint8_t> def_buf;
+        bool any_var = false;
         bool eligible = dc_on && req->n_output_offsets > 0;
         for (uint32_t oo = 0; eligible && oo < req->n_output_offsets; oo++) {
           uint32_t off = req->output_offsets[oo];
@@ -3139,10 +3178,61 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
               cs.is_real = 0; break;
             case COPR_TP_DOUBLE: cs.is_real = 1; break;
             case COPR_TP_DURATION: cs.is_real = 2; break;
+            case COPR_TP_VARCHAR: case COPR_TP_VARSTRING: case COPR_TP_STRING:
+            case COPR_TP_BLOB:
+              ctypes[oo] = 1; break;
+            case COPR_TP_NEWDECIMAL: ctypes[oo] = 2; break;
             default: eligible = false;
           }
           if (!eligible) break;
-          if (pl.sp.out_is_handle[off]) {
+          if (ctypes[oo]) {
+            /* always the cell itself: no decode channel carries bytes or
+               decimals */
+            const CoprColumnInfo &ci = pl.cols[off];
+            if (pl.sp.out_is_handle[off] ||
+                ((int)off == pl.dec2_col_offset && pl.sp.dec2_col_id) ||
+                ((int)off == pl.filter_col_offset && pl.sp.has_filter)) {
+              eligible = false;
+              break;
+            }
+            any_var = true;
+            cs.kind = 0;
+            cs.j = (int32_t)off;
+            if (ci.default_val && ci.default_val_len) {
+              /* the default datum, decoded once into its chunk form exactly
+                 as e_chunk_append_datum would decode it from the response */
+              const uint8_t *dp = ci.default_val;
+              size_t dl = ci.default_val_len;
+              if (dp[0] == 0 && dl == 1) {
+                cs.missing_null = 1;
+              } else if (ctypes[oo] == 1 && dp[0] == 2) {
+                uint64_t uv;
+                size_t nb;
+                if (!e_var_u64(dp + 1, dl - 1, &uv, &nb) || (uv & 1) ||
+                    1 + nb + (uv >> 1) != dl) { eligible = false; break; }
+                def_off[oo] = (uint32_t)def_buf.size();
+                def_len[oo] = (uint32_t)(uv >> 1);
+                def_buf.insert(def_buf.end(), dp + 1 + nb, dp + dl);
+              } else if (ctypes[oo] == 2 && dp[0] == 6) {
+                prod::PDec d;
+                uint8_t rf = 0, buf[40];
+                size_t used = 0;
+                if (!prod::pdec_decode(dp + 1, dl - 1, &d, &rf, &used) ||
+                    1 + used != dl) { eligible = false; break; }
+                e_dec_chunk_struct(d, rf, buf);
+                def_off[oo] = (uint32_t)def_buf.size();
+                def_len[oo] = 40;
+                def_buf.insert(def_buf.end(), buf, buf + 40);
+              } else {
+                eligible = false;
+                break;
+              }
+            } else if (!(ci.ft.flag & COPR_FLAG_NOT_NULL)) {
+              cs.missing_null = 1;
+            } else {
+              eligible = false;
+            }
+          } else if (pl.sp.out_is_handle[off]) {
             cs.kind = 1;
           } else if ((int)off == pl.dec2_col_offset && pl.sp.dec2_col_id) {
             cs.kind = 3;
@@ -3220,13 +3310,32 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             }
           }
           std::vector<uint8_t> chunk_bytes;
-          int rc = copr::dev_chunk_encode(po, r->dev,
-                                          pl.sp.index_mode != 0, scan_end_l,
-                                          specs.data(),
-                                          (int)req->n_output_offsets,
-                                          pl.sp.n_out, cr_l, eng->stream,
-                                          &chunk_bytes);
+          int rc;
+          if (any_var) {
+            std::vector<copr::ChunkVarSpec> vspecs(req->n_output_offsets);
+            for (uint32_t oo = 0; oo < req->n_output_offsets; oo++) {
+              vspecs[oo].fx = specs[oo];
+              vspecs[oo].ctype = ctypes[oo];
+              vspecs[oo].def_off = def_off[oo];
+              vspecs[oo].def_len = def_len[oo];
+              vspecs[oo].vidx = -1;
+            }
+            rc = copr::dev_chunk_encode_var(po, r->dev, pl.sp.index_mode != 0,
+                                            scan_end_l, vspecs.data(),
+                                            (int)req->n_output_offsets,
+                                            pl.sp.n_out, def_buf.data(),
+                                            def_buf.size(), cr_l, eng->stream,
+                                            &chunk_bytes);
+          } else {
+            rc = copr::dev_chunk_encode(po, r->dev,
+                                        pl.sp.index_mode != 0, scan_end_l,
+                                        specs.data(),
+                                        (int)req->n_output_offsets,
+                                        pl.sp.n_out, cr_l, eng->stream,
+                                        &chunk_bytes);
+          }
           if (rc == 0) {
+            eng->dev_chunk_runs++;
             free_po();
             resp.insert(resp.end(), chunk_bytes.begin(), chunk_bytes.end());
             for (uint64_t cn : cr_l) n_rows_out += cn;

@@ -504,6 +504,28 @@ int dev_chunk_encode(const ProjectOut &po, const DevRegion &rgn, int idxp,
                      int n_cols, int n_out,
                      const std::vector<uint64_t> &chunk_rows, void *stream,
                      std::vector<uint8_t> *out_resp);
+/* device TypeChunk encode for schemas with bytes / decimal output columns
+ * (chunk_var.hip). A fixed-8 column is sourced by fx exactly as
+ * dev_chunk_encode sources it; a bytes or decimal column is always a cell
+ * (fx.kind 0) and uses fx.j and fx.missing_null only. */
+/* payload tile of k_cv_payload: 20 KiB of LDS per block less the row
+   descriptors and the alignment slack */
+#define COPR_CHUNK_TILE_BYTES 15856u
+struct ChunkVarSpec {
+  ChunkColSpec fx;
+  int32_t ctype;        /* 0 fixed-8, 1 bytes, 2 decimal */
+  uint32_t def_off;     /* missing column with a default: its chunk form in */
+  uint32_t def_len;     /* the defaults buffer (payload / 40-byte struct) */
+  int32_t vidx;         /* bytes column: its index among the bytes columns
+                           (filled in by dev_chunk_encode_var) */
+};
+/* same return codes as dev_chunk_encode; defaults: def_bytes host bytes */
+int dev_chunk_encode_var(const ProjectOut &po, const DevRegion &rgn, int idxp,
+                         uint64_t scan_end, const ChunkVarSpec *h_specs,
+                         int n_cols, int n_out, const uint8_t *defaults,
+                         size_t def_bytes,
+                         const std::vector<uint64_t> &chunk_rows, void *stream,
+                         std::vector<uint8_t> *out_resp);
 int dev_mvcc_build(const uint8_t *d_keys, const uint64_t *d_ko,
                    const uint8_t *d_vals, const uint64_t *d_vo, uint64_t n,
                    const uint8_t *dd_keys, const uint64_t *dd_ko,
@@ -549,6 +571,8 @@ struct copr_engine {
   uint64_t group_last_groups = 0;
   uint64_t group_dict_grows = 0;
   uint64_t group_row_source_runs = 0;
+  /* copr_engine_dev_chunk_runs */
+  uint64_t dev_chunk_runs = 0;
   /* RCCL communicator state (copr_comm.cpp); null until copr_comm_create */
   void *comm_state = nullptr;
   /* hash-agg table cache: the per-request hipMalloc/hipFree set measured

@@ -595,6 +595,11 @@ class Engine:
                 self._lib.copr_engine_group_dict_grows(self._h),
                 self._lib.copr_engine_group_row_source_runs(self._h))
 
+    def dev_chunk_runs(self):
+        """Chunked project responses built on the device since the engine was
+        created; one that fell back to the host re-encode is not counted."""
+        return self._lib.copr_engine_dev_chunk_runs(self._h)
+
     def close(self):
         if self._h:
             self._lib.copr_engine_destroy(self._h)
