@@ -111,6 +111,12 @@ uint64_t    copr_engine_narrow_launches(const copr_engine *);
 uint64_t    copr_engine_narrow_builds(const copr_engine *);
 /* of the narrow launches, those over a split plane */
 uint64_t    copr_engine_split_launches(const copr_engine *);
+/* The one-dispatch filter+count step: requests whose end the
+ * host learnt from the sequence word it polled, and requests that waited for
+ * the stream instead (deadline passed, or COPR_FC_POLL_US=0). Monotonic;
+ * requests of every other branch move neither. */
+uint64_t    copr_engine_fc_polled(const copr_engine *);
+uint64_t    copr_engine_fc_fallbacks(const copr_engine *);
 /* TopN over several order-by columns: requests served by the
  * multi-key pipeline (monotonic), and for the last of them the rows its
  * filters kept (m) and the rows that passed the primary-key candidate cut

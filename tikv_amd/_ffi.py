@@ -170,6 +170,10 @@ def load_lib():
     lib.copr_engine_narrow_builds.argtypes = [C.c_void_p]
     lib.copr_engine_split_launches.restype = C.c_uint64
     lib.copr_engine_split_launches.argtypes = [C.c_void_p]
+    lib.copr_engine_fc_polled.restype = C.c_uint64
+    lib.copr_engine_fc_polled.argtypes = [C.c_void_p]
+    lib.copr_engine_fc_fallbacks.restype = C.c_uint64
+    lib.copr_engine_fc_fallbacks.argtypes = [C.c_void_p]
     lib.copr_engine_topn_multi_runs.restype = C.c_uint64
     lib.copr_engine_topn_multi_runs.argtypes = [C.c_void_p]
     lib.copr_engine_topn_last_kept.restype = C.c_uint64

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/copr_gpu.h"
 #include "copr_internal.h"
+#include "fc_wait.h"
 #include "prod_decimal.h"
 
 #include <cstring>
@@ -65,6 +66,9 @@ extern "C" copr_status copr_engine_create(int hip_device, copr_engine **out) {
 
 extern "C" void copr_engine_destroy(copr_engine *eng) {
   if (!eng) return;
+  /* a polled filter+count request returns with its launch not yet retired
+     (DESIGN §9n): nothing the kernel may still touch is freed under it */
+  if (eng->stream) (void)hipStreamSynchronize(eng->stream);
   copr::comm_free(eng);
   if (eng->d_crc_tables) hipFree(eng->d_crc_tables);
   {
@@ -105,6 +109,14 @@ extern "C" uint64_t copr_engine_narrow_builds(const copr_engine *eng) {
 
 extern "C" uint64_t copr_engine_split_launches(const copr_engine *eng) {
   return eng ? eng->split_launches : 0;
+}
+
+extern "C" uint64_t copr_engine_fc_polled(const copr_engine *eng) {
+  return eng ? eng->fc_polled : 0;
+}
+
+extern "C" uint64_t copr_engine_fc_fallbacks(const copr_engine *eng) {
+  return eng ? eng->fc_fallbacks : 0;
 }
 
 extern "C" uint64_t copr_engine_topn_multi_runs(const copr_engine *eng) {
@@ -2344,6 +2356,10 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
   hipEvent_t ev_a = eng->ev_a, ev_b = eng->ev_b;
   float kernel_ms = 0.0f;
   bool timed = false;
+  /* the one-dispatch filter+count step records no events: its kernel reports
+     its own duration */
+  uint64_t kernel_ns = 0;
+  bool own_time = false;
 
   if (pl.has_topn) {
     /* ---- TopN: winner selection on device, then the regular project path
@@ -2671,18 +2687,30 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
       if (one_dispatch && !eng->d_fcn_state) {
         /* first use; on failure the request takes the usual sequence */
         void *d = nullptr, *h = nullptr;
+        /* coherent by request: the words are polled while the kernel runs */
         if (hipMalloc(&d, COPR_FCN_STATE_WORDS * 8) == hipSuccess &&
-            hipHostMalloc(&h, sizeof(unsigned long long),
-                          hipHostMallocDefault) == hipSuccess) {
+            hipHostMalloc(&h, FCW_WORDS * sizeof(unsigned long long),
+                          hipHostMallocCoherent) == hipSuccess) {
+          memset(h, 0, FCW_WORDS * sizeof(unsigned long long));
           eng->d_fcn_state = (unsigned long long *)d;
           eng->h_fcn_out = (unsigned long long *)h;
           eng->fcn_dirty = true;          /* zeroed below */
+          int khz = 0;
+          if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate,
+                                    eng->device) != hipSuccess || khz < 0) {
+            (void)hipGetLastError();
+            khz = 0;
+          }
+          eng->wall_khz = (uint32_t)khz;
         } else {
           (void)hipGetLastError();
           hipFree(d);
           one_dispatch = false;
         }
       }
+      /* without the clock's rate the ticks mean nothing: such an engine keeps
+         the event-timed sequence, which reports a kernel time */
+      if (one_dispatch && !eng->wall_khz) one_dispatch = false;
       if (one_dispatch && eng->fcn_dirty) {
         if (hipMemsetAsync(eng->d_fcn_state, 0, COPR_FCN_STATE_WORDS * 8,
                            eng->stream) == hipSuccess) {
@@ -2698,7 +2726,15 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         unsigned long long *d_cnt = eng->d_fcn_state;
         unsigned int *d_ticket = (unsigned int *)(
             eng->d_fcn_state + COPR_FCN_SLOTS * COPR_FCN_SLOT_STRIDE);
-        hipEventRecord(ev_a, eng->stream);
+        /* No events and no stream wait: the first launch stamps
+           the start, the last one's last block hands over count, ticks and
+           this request's sequence number, and the host waits for the
+           number. */
+        unsigned long long *d_stamp =
+            (unsigned long long *)d_ticket + COPR_FCN_STAMP_WORD;
+        if (!++eng->fcn_seq) ++eng->fcn_seq;
+        const unsigned long long seq = eng->fcn_seq;
+        uint64_t stream_bytes = 0;
         for (uint32_t rg = 0; rg < n_regions; rg++) {
           const bool last = rg + 1 == n_regions;
           int e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf, nuse[rg].sf,
@@ -2706,6 +2742,7 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
                                        COPR_FCN_SLOTS,
                                        last ? d_ticket : nullptr,
                                        last ? eng->h_fcn_out : nullptr,
+                                       rg == 0 ? d_stamp : nullptr, seq,
                                        fcn_grid, eng->stream);
           eng->plane_launches++;
           eng->narrow_launches++;
@@ -2714,16 +2751,40 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             eng->fcn_dirty = true;
             return SET_ERR(COPR_ERR_INTERNAL, "narrow plane launch failed");
           }
+          stream_bytes += regions[rg]->dev.n_kv * nuse[rg].p->nar_w;
         }
-        hipEventRecord(ev_b, eng->stream);
-        timed = true;
-        hipError_t ce = hipStreamSynchronize(eng->stream);
-        if (ce != hipSuccess) {
-          eng->fcn_dirty = true;
-          return SET_ERR(COPR_ERR_INTERNAL, hipGetErrorString(ce));
+        /* How long to spin before handing the wait to the runtime: the bytes
+           the launches can read (a split plane's both halves) at 50 GB/s, a
+           hundredth of the slowest rate a plane has shown (5
+           TB/s), plus 2 ms for the launches to reach a device that other
+           work holds. Past it, or with COPR_FC_POLL_US=0 (read per call), the
+           request waits for the stream as it always did: the deadline only
+           chooses who waits, the words are read after either wait. */
+        uint64_t poll_us = stream_bytes / 50000u + 2000u;
+        if (const char *pe = getenv("COPR_FC_POLL_US"))
+          poll_us = (uint64_t)strtoull(pe, nullptr, 10);
+        const volatile uint64_t *hw = (const volatile uint64_t *)eng->h_fcn_out;
+        if (wait_seq(hw, seq, poll_us) == FCW_ARRIVED) {
+          eng->fc_polled++;
+        } else {
+          eng->fc_fallbacks++;
+          hipError_t ce = hipStreamSynchronize(eng->stream);
+          if (ce == hipSuccess &&
+              __atomic_load_n((const uint64_t *)&hw[FCW_SEQ],
+                              __ATOMIC_ACQUIRE) != seq) {
+            eng->fcn_dirty = true;
+            return SET_ERR(COPR_ERR_INTERNAL,
+                           "filter+count finished without its sequence word");
+          }
+          if (ce != hipSuccess) {
+            eng->fcn_dirty = true;
+            return SET_ERR(COPR_ERR_INTERNAL, hipGetErrorString(ce));
+          }
         }
         memset(h_acc, 0, sizeof(h_acc));
-        h_acc[0].cnt = *(volatile unsigned long long *)eng->h_fcn_out;
+        h_acc[0].cnt = hw[FCW_COUNT];
+        kernel_ns = ticks_to_ns(hw[FCW_TICKS], eng->wall_khz);
+        own_time = true;
       } else {
         HIP_TRY(hipMemsetAsync(d_acc, 0,
                                sizeof(SimpleAggAcc) * (COPR_MAX_AGGS + 1),
@@ -2744,7 +2805,8 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
                count joins the other regions' in the usual accumulator */
             e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf, nuse[rg].sf,
                                      regions[rg]->dev.n_kv, &d_acc[0].cnt, 1,
-                                     nullptr, nullptr, fcn_grid, eng->stream);
+                                     nullptr, nullptr, nullptr, 0, fcn_grid,
+                                     eng->stream);
             eng->plane_launches++;
             eng->narrow_launches++;
             if (nuse[rg].p->nar_lo_off) eng->split_launches++;
@@ -3591,7 +3653,8 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
   out->n_summaries = req->n_executors;
   if (out->n_summaries) {
     out->summaries[out->n_summaries - 1].num_produced_rows = n_rows_out;
-    out->summaries[0].time_processed_ns = (uint64_t)(kernel_ms * 1e6);
+    out->summaries[0].time_processed_ns =
+        own_time ? kernel_ns : (uint64_t)(kernel_ms * 1e6);
     out->summaries[0].num_iterations = 1;
   }
   return COPR_OK;

@@ -370,19 +370,26 @@ bool dev_plane_fc_shape(const ScanPlan &plan, const PlaneSet &ps,
 /* filter+count over a narrow plane (narrow_planes.hip): adds the kept rows
  * to n_slots count words (a power of two <= COPR_FCN_SLOTS), the first at
  * d_cnt and COPR_FCN_SLOT_STRIDE words apart; their sum is the count. With a
- * non-null d_ticket the launch finalizes: its last block stores that sum to
- * *h_out (device-visible pinned host memory) and zeroes the count words and
- * *d_ticket. grid_cap 0 = the default grid. A split plane
- * (width 4) takes k_plane_fcs and sf, the others k_plane_fcn<T> and nf. */
+ * non-null d_ticket the launch finalizes: its last block stores that sum,
+ * the request's wall-clock ticks and last of all seq (never 0) to the three
+ * words at h_out (fc_wait.h FCW_*; fine-grained pinned host memory) and
+ * zeroes the count words, *d_ticket and the stamp word.
+ * A non-null d_stamp marks the launch that opens a request: its block 0
+ * leaves the wall clock it read at entry in that word, which is the u64
+ * COPR_FCN_STAMP_WORD behind the ticket. grid_cap 0 = the default grid. A
+ * split plane (width 4) takes k_plane_fcs and sf, the others k_plane_fcn<T>
+ * and nf. */
 #define COPR_FCN_SLOTS 64
 #define COPR_FCN_SLOT_STRIDE 16          /* u64 words: one 128 B line each */
 #define COPR_FCN_STATE_WORDS (COPR_FCN_SLOTS * COPR_FCN_SLOT_STRIDE + 16)
+#define COPR_FCN_STAMP_WORD 1            /* u64 words behind the ticket */
 int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
                          const SplitFcArgs &sf, uint64_t n_rows,
                          unsigned long long *d_cnt,
                          uint32_t n_slots, unsigned int *d_ticket,
-                         unsigned long long *h_out, uint32_t grid_cap,
-                         void *stream);
+                         unsigned long long *h_out,
+                         unsigned long long *d_stamp, unsigned long long seq,
+                         uint32_t grid_cap, void *stream);
 /* simple aggregates (mode 1) over column planes instead of the row bytes */
 int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
                          const DevRegion &rgn, SimpleAggAcc *d_simple,
@@ -587,14 +594,21 @@ struct copr_engine {
      memsets, freed in engine destroy */
   copr::SimpleAggAcc *d_simple_acc = nullptr;
   unsigned long long *d_simple_ext = nullptr;
-  /* one-dispatch filter+count over narrow planes: the device
-     count words and, behind them, the ticket word (COPR_FCN_STATE_WORDS u64
-     in all), zero between requests because the finalizing block resets
-     them, and the pinned host
-     word that block delivers the total to. fcn_dirty = a HIP call on that
-     path failed, so the words are memset before their next use. */
+  /* one-dispatch filter+count over narrow planes: the
+     device count words and, behind them, the ticket word and the start
+     stamp (COPR_FCN_STATE_WORDS u64 in all), zero between requests because
+     the finalizing block resets them, and the three pinned host words
+     (fc_wait.h FCW_*, fine-grained: the host polls them while the kernel
+     runs) that block delivers count, ticks and the request's sequence number
+     to. fcn_seq = the last number handed out; never 0, so the zeroed area
+     matches no request. fcn_dirty = a HIP call on that path failed, so the
+     device words are memset before their next use. wall_khz = the device's
+     wall-clock rate, queried with the allocation; 0 = unknown, and the
+     engine's requests then keep the event-timed sequence. */
   unsigned long long *d_fcn_state = nullptr;
   unsigned long long *h_fcn_out = nullptr;
+  unsigned long long fcn_seq = 0;
+  uint32_t wall_khz = 0;
   bool fcn_dirty = false;
   /* the event pair copr_dag_run times its launches with: created on the
      first request (ev_tried = that has happened, whatever came of it), kept
@@ -611,6 +625,10 @@ struct copr_engine {
   uint64_t narrow_launches = 0;
   uint64_t narrow_builds = 0;
   uint64_t split_launches = 0;     /* narrow launches that took k_plane_fcs */
+  /* one-dispatch requests that ended on the polled word / on the stream wait
+     (copr_engine_fc_polled / _fc_fallbacks) */
+  uint64_t fc_polled = 0;
+  uint64_t fc_fallbacks = 0;
 };
 
 struct copr_region {

@@ -3,6 +3,7 @@
  * and their consumers live in kernels.hip. */
 #include <hip/hip_runtime.h>
 #include "copr_internal.h"
+#include "fc_wait.h"                     /* FCW_* host word indices */
 
 namespace copr {
 
@@ -187,13 +188,38 @@ const DevRegion::ColPlane *dev_colplane_narrow(DevRegion &rgn, int64_t col_id,
  * not.
  * With a ticket the launch finalizes the request: lane 0 of each block draws
  * a ticket once its add has returned, and the block that draws the last one
- * collects the count words, hands the total to the host and leaves words and
- * ticket zero for the next request. Only atomics touch these words, so no
- * cache has to be written back or invalidated. */
+ * collects the count words, hands the host its three words and leaves count
+ * words, ticket and stamp zero for the next request. Only atomics touch these
+ * words, so no cache has to be written back or invalidated.
+ * The request times itself. The launch that opens it has a
+ * non-null stamp, the word COPR_FCN_STAMP_WORD behind the ticket, and its
+ * block 0 reads the wall clock at entry (fcn_entry_clock) and stores it there
+ * from this tail, so no wave waits for a round trip before its first loads.
+ * When that launch also finalizes, the store is performed before block 0
+ * draws its ticket, by the rule of the count add: an atomic with a return
+ * value, waited for; relaxed atomics to two addresses are not ordered
+ * otherwise. The finalizing block takes the stamp back, reads the clock again
+ * and stores to h_out, fine-grained pinned host memory the host polls:
+ * FCW_COUNT and FCW_TICKS, a system-scope fence, then seq in FCW_SEQ, which
+ * the host waits for, and a second fence. seq is never 0 and new for every
+ * request.
+ * Assumption: block 0 starts no later than any other block's first load
+ * matters. Workgroups are handed out in index order, so block 0 is in the
+ * first wave of dispatches; the time between the dispatch packet and block
+ * 0's first instruction is not in the figure (measured against the tracer's
+ * durations in DESIGN §9n). */
+__device__ __forceinline__ unsigned long long
+fcn_entry_clock(const unsigned long long *stamp) {
+  /* block-uniform, so the value lives in scalar registers through the loop */
+  return (stamp && blockIdx.x == 0) ? wall_clock64() : 0ull;
+}
+
 __device__ __forceinline__ void
 fcn_block_count(unsigned long long cnt, unsigned long long *__restrict__ cnt_out,
                 uint32_t slot_mask, unsigned int *__restrict__ ticket,
-                unsigned long long *__restrict__ h_out) {
+                unsigned long long *__restrict__ h_out,
+                unsigned long long *__restrict__ stamp,
+                unsigned long long t_entry, unsigned long long seq) {
   __shared__ unsigned long long s_cnt[4];
   __shared__ unsigned int s_last;
   for (int off = 32; off > 0; off >>= 1)
@@ -205,15 +231,21 @@ fcn_block_count(unsigned long long cnt, unsigned long long *__restrict__ cnt_out
     unsigned long long *slot =
         cnt_out + (size_t)(blockIdx.x & slot_mask) * COPR_FCN_SLOT_STRIDE;
     unsigned int last = 0;
+    /* the stamp and the add are in flight together; each has been performed
+       once its old value is back, and one wait covers both. Without a ticket
+       nobody waits: a later launch of the request is behind this one in the
+       stream */
+    unsigned long long old_s = 0, old_c = 0;
+    if (stamp && blockIdx.x == 0)
+      old_s = __hip_atomic_exchange(stamp, t_entry, __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
     if (!ticket) {
       if (b) atomicAdd(slot, b);
     } else {
-      if (b) {
-        /* the add has been performed once its old value is back */
-        unsigned long long old = __hip_atomic_fetch_add(
-            slot, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" :: "v"(old) : "memory");
-      }
+      if (b)
+        old_c = __hip_atomic_fetch_add(slot, b, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" :: "v"(old_s), "v"(old_c) : "memory");
       unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_AGENT);
       last = t == gridDim.x - 1 ? 1u : 0u;
@@ -223,8 +255,15 @@ fcn_block_count(unsigned long long cnt, unsigned long long *__restrict__ cnt_out
   if (!ticket) return;
   __syncthreads();
   if (!s_last || threadIdx.x >= 64u) return;
-  /* every block's add returned before its ticket was drawn, and this block
-     drew the last ticket: the words are final */
+  /* every block's add, and block 0's stamp, returned before its ticket was
+     drawn, and this block drew the last ticket: the words are final */
+  /* lane 0 takes the stamp back in the same breath as the lanes take the
+     count words, so the two round trips overlap and the tail waits once */
+  unsigned long long t0 = 0;
+  if (threadIdx.x == 0)
+    t0 = __hip_atomic_exchange(
+        (unsigned long long *)ticket + COPR_FCN_STAMP_WORD, 0ull,
+        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   unsigned long long tot = 0;
   if (threadIdx.x <= slot_mask)
     tot = __hip_atomic_exchange(
@@ -233,8 +272,17 @@ fcn_block_count(unsigned long long cnt, unsigned long long *__restrict__ cnt_out
   for (int off = 32; off > 0; off >>= 1)
     tot += (unsigned long long)__shfl_down((long long)tot, off, 64);
   if (threadIdx.x == 0) {
+    const unsigned long long t1 = wall_clock64();
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *(volatile unsigned long long *)h_out = tot;
+    __hip_atomic_store(h_out + FCW_COUNT, tot, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
+    /* a clock that did not advance reads as "no time", never as a wrapped
+       difference */
+    __hip_atomic_store(h_out + FCW_TICKS, t1 > t0 ? t1 - t0 : 0ull,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
+    __hip_atomic_store(h_out + FCW_SEQ, seq, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
     __threadfence_system();
   }
 }
@@ -279,7 +327,9 @@ __global__ void __launch_bounds__(256)
 k_plane_fcn(const uint4 *__restrict__ data, uint64_t n_rows, NarrowFcArgs nf,
             unsigned long long *__restrict__ cnt_out, uint32_t slot_mask,
             unsigned int *__restrict__ ticket,
-            unsigned long long *__restrict__ h_out) {
+            unsigned long long *__restrict__ h_out,
+            unsigned long long *__restrict__ stamp, unsigned long long seq) {
+  const unsigned long long t_entry = fcn_entry_clock(stamp);
   constexpr int UNR = 4;
   constexpr uint32_t R = 16u / sizeof(T);          /* rows per 16 B */
   constexpr uint32_t PW = 4u / sizeof(T);          /* rows per 32-bit word */
@@ -340,7 +390,7 @@ k_plane_fcn(const uint4 *__restrict__ data, uint64_t n_rows, NarrowFcArgs nf,
     }
     cnt += c;
   }
-  fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out);
+  fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out, stamp, t_entry, seq);
 }
 
 /* Filter+count over a split plane: k_plane_fcn's shape over the
@@ -362,7 +412,9 @@ k_plane_fcs(const uint4 *__restrict__ hi, const uint4 *__restrict__ lo,
             uint64_t n_rows, SplitFcArgs sf,
             unsigned long long *__restrict__ cnt_out, uint32_t slot_mask,
             unsigned int *__restrict__ ticket,
-            unsigned long long *__restrict__ h_out) {
+            unsigned long long *__restrict__ h_out,
+            unsigned long long *__restrict__ stamp, unsigned long long seq) {
+  const unsigned long long t_entry = fcn_entry_clock(stamp);
   constexpr int UNR = 4;
   constexpr uint32_t R = 8;                        /* rows per 16 B */
   const bool inv = sf.invert != 0;
@@ -475,16 +527,22 @@ k_plane_fcs(const uint4 *__restrict__ hi, const uint4 *__restrict__ lo,
     }
     cnt += inv ? __popc(livem) - in : in;
   }
-  fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out);
+  fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out, stamp, t_entry, seq);
 }
 
 int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
                          const SplitFcArgs &sf, uint64_t n_rows,
                          unsigned long long *d_cnt,
                          uint32_t n_slots, unsigned int *d_ticket,
-                         unsigned long long *h_out, uint32_t grid_cap,
-                         void *stream) {
-  if (!p.nar || (d_ticket && !h_out) || !n_slots || n_slots > 64 ||
+                         unsigned long long *h_out,
+                         unsigned long long *d_stamp, unsigned long long seq,
+                         uint32_t grid_cap, void *stream) {
+  /* a stamp is taken back by a finalizing launch alone, and its word sits
+     behind the ticket */
+  if (d_stamp && d_ticket &&
+      d_stamp != (unsigned long long *)d_ticket + COPR_FCN_STAMP_WORD)
+    return -1;
+  if (!p.nar || (d_ticket && (!h_out || !seq)) || !n_slots || n_slots > 64 ||
       (n_slots & (n_slots - 1)) || (p.nar_w == 4) != (p.nar_lo_off != 0))
     return -1;
   hipStream_t s = (hipStream_t)stream;
@@ -506,16 +564,18 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
   switch (p.nar_w) {
     case 1:
       hipLaunchKernelGGL(k_plane_fcn<uint8_t>, dim3((uint32_t)nb), dim3(256),
-                         0, s, data, n_rows, nf, d_cnt, mask, d_ticket, h_out);
+                         0, s, data, n_rows, nf, d_cnt, mask, d_ticket, h_out,
+                         d_stamp, seq);
       break;
     case 2:
       hipLaunchKernelGGL(k_plane_fcn<uint16_t>, dim3((uint32_t)nb), dim3(256),
-                         0, s, data, n_rows, nf, d_cnt, mask, d_ticket, h_out);
+                         0, s, data, n_rows, nf, d_cnt, mask, d_ticket, h_out,
+                         d_stamp, seq);
       break;
     case 4:
       hipLaunchKernelGGL(k_plane_fcs, dim3((uint32_t)nb), dim3(256), 0, s, data,
                          (const uint4 *)((const uint8_t *)p.nar + p.nar_lo_off),
-                         n_rows, sf, d_cnt, mask, d_ticket, h_out);
+                         n_rows, sf, d_cnt, mask, d_ticket, h_out, d_stamp, seq);
       break;
     default:
       return -1;

@@ -575,6 +575,14 @@ class Engine:
         a split plane, i.e. took k_plane_fcs, since the engine was created."""
         return self._lib.copr_engine_split_launches(self._h)
 
+    def fc_wait_stats(self):
+        """(polled, fallbacks): one-dispatch filter+count requests whose end
+        the host learnt from the polled sequence word, and those that waited
+        for the stream instead (COPR_FC_POLL_US=0 or a passed deadline),
+        since the engine was created. Other branches move neither."""
+        return (self._lib.copr_engine_fc_polled(self._h),
+                self._lib.copr_engine_fc_fallbacks(self._h))
+
     def topn_stats(self):
         """(runs, kept, candidates): TopN requests served by the multi-key
         pipeline since the engine was created, and for the last of them the
