@@ -117,6 +117,12 @@ uint64_t    copr_engine_split_launches(const copr_engine *);
  * requests of every other branch move neither. */
 uint64_t    copr_engine_fc_polled(const copr_engine *);
 uint64_t    copr_engine_fc_fallbacks(const copr_engine *);
+/* IN-list filters over column planes: per-region launches of
+ * the set-probe kernel over the wide planes and of the bitmap filter+count
+ * kernel over a 1- or 2-byte narrow plane (copr_engine_plane_launches counts
+ * both too). Monotonic. */
+void        copr_engine_in_launches(const copr_engine *, uint64_t *wide,
+                                    uint64_t *bitmap);
 /* TopN over several order-by columns: requests served by the
  * multi-key pipeline (monotonic), and for the last of them the rows its
  * filters kept (m) and the rows that passed the primary-key candidate cut

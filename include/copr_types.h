@@ -101,7 +101,19 @@ enum CoprScalarSig {
   COPR_SIG_EQ_REAL, COPR_SIG_NE_REAL,
   COPR_SIG_LOGICAL_AND, COPR_SIG_LOGICAL_OR, COPR_SIG_UNARY_NOT,
   COPR_SIG_PLUS_INT, COPR_SIG_MINUS_INT, COPR_SIG_MULTIPLY_INT,
-  COPR_SIG_INT_IS_NULL, COPR_SIG_INT_IS_TRUE, COPR_SIG_INT_IS_FALSE
+  COPR_SIG_INT_IS_NULL, COPR_SIG_INT_IS_TRUE, COPR_SIG_INT_IS_FALSE,
+  /* col IN (c1, ..., cn), tipb InInt. RPN form: probe, item_1, ..., item_n,
+   * func(IN_INT, n_args = n + 1). NULL when the probe is NULL; 1 when the
+   * probe equals a non-NULL item as an integer (the column read under its
+   * UNSIGNED flag, each item under its kind, so equal bit patterns of
+   * different signedness match only when non-negative); otherwise NULL when
+   * an item is NULL, else 0. Hence NOT IN over a list with a NULL keeps no
+   * row. First slice: the probe is one COLUMN_REF to an int
+   * column that is not a pk handle, the items are CONST_INT, CONST_UINT or
+   * CONST_NULL, 1 to 1024 of them, and a selection holds at most one IN
+   * node; anything else is COPR_ERR_UNSUPPORTED, n_args < 2
+   * COPR_ERR_INVALID_REQUEST. */
+  COPR_SIG_IN_INT = 22
 };
 
 typedef struct CoprExprNode {

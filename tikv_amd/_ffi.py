@@ -96,7 +96,8 @@ EXPR_COLUMN_REF, EXPR_CONST_NULL, EXPR_CONST_INT, EXPR_CONST_UINT, \
  SIG_LT_REAL, SIG_LE_REAL, SIG_GT_REAL, SIG_GE_REAL, SIG_EQ_REAL, SIG_NE_REAL,
  SIG_LOGICAL_AND, SIG_LOGICAL_OR, SIG_UNARY_NOT,
  SIG_PLUS_INT, SIG_MINUS_INT, SIG_MULTIPLY_INT,
- SIG_INT_IS_NULL, SIG_INT_IS_TRUE, SIG_INT_IS_FALSE) = range(1, 22)
+ SIG_INT_IS_NULL, SIG_INT_IS_TRUE, SIG_INT_IS_FALSE,
+ SIG_IN_INT) = range(1, 23)
 
 (AGG_COUNT, AGG_SUM, AGG_AVG, AGG_MAX, AGG_MIN, AGG_FIRST,
  AGG_BIT_AND, AGG_BIT_OR, AGG_BIT_XOR) = range(9)
@@ -174,6 +175,9 @@ def load_lib():
     lib.copr_engine_fc_polled.argtypes = [C.c_void_p]
     lib.copr_engine_fc_fallbacks.restype = C.c_uint64
     lib.copr_engine_fc_fallbacks.argtypes = [C.c_void_p]
+    lib.copr_engine_in_launches.restype = None
+    lib.copr_engine_in_launches.argtypes = [C.c_void_p, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64)]
     lib.copr_engine_topn_multi_runs.restype = C.c_uint64
     lib.copr_engine_topn_multi_runs.argtypes = [C.c_void_p]
     lib.copr_engine_topn_last_kept.restype = C.c_uint64

@@ -80,6 +80,7 @@ extern "C" void copr_engine_destroy(copr_engine *eng) {
   hipFree(eng->d_simple_acc);
   hipFree(eng->d_simple_ext);
   hipFree(eng->d_fcn_state);
+  hipFree(eng->d_in_tab);
   if (eng->h_fcn_out) hipHostFree(eng->h_fcn_out);
   if (eng->ev_a) hipEventDestroy(eng->ev_a);
   if (eng->ev_b) hipEventDestroy(eng->ev_b);
@@ -109,6 +110,12 @@ extern "C" uint64_t copr_engine_narrow_builds(const copr_engine *eng) {
 
 extern "C" uint64_t copr_engine_split_launches(const copr_engine *eng) {
   return eng ? eng->split_launches : 0;
+}
+
+extern "C" void copr_engine_in_launches(const copr_engine *eng, uint64_t *wide,
+                                        uint64_t *bitmap) {
+  if (wide) *wide = eng ? eng->in_wide_launches : 0;
+  if (bitmap) *bitmap = eng ? eng->in_bitmap_launches : 0;
 }
 
 extern "C" uint64_t copr_engine_fc_polled(const copr_engine *eng) {
@@ -853,6 +860,14 @@ struct HostPlan {
   /* offsets of the third and fourth column an RPN selection names (the
      extra-capture channels), -1 = none */
   int xcap_col_offset[2] = {-1, -1};
+  /* IN-list predicate: the host image of the selection's one IN
+     node; in_simple = the selection is exactly in(col, ...) or
+     not(in(col, ...)), the shape the set-probe plane kernels take, in_negate
+     = the latter */
+  bool has_in = false;
+  bool in_simple = false;
+  bool in_negate = false;
+  copr::InSet in_set;
   uint64_t limit = UINT64_MAX;
 };
 
@@ -1075,6 +1090,24 @@ static bool plane_plan_ok(const ScanPlan &sp) {
   return any_col;
 }
 
+/* the same, with the keep decision in(col, ...) or
+   not(in(col, ...)) over one column: k_plane_in / k_plane_inb */
+static bool in_plane_plan_ok(const HostPlan &pl) {
+  const ScanPlan &sp = pl.sp;
+  if (!pl.in_simple || sp.mode != 1 || sp.index_mode || !sp.rpn_on ||
+      !sp.has_filter || sp.filter2_on || sp.n_xcap || sp.filter_decode_only ||
+      sp.dec2_col_id)
+    return false;
+  for (int a = 0; a < sp.n_aggs; a++) {
+    switch (sp.aggs[a].kind) {
+      case DAGG_COUNT_ROWS: case DAGG_COUNT_COL: case DAGG_SUM_INT:
+      case DAGG_MAX_INT: case DAGG_MIN_INT: break;
+      default: return false;
+    }
+  }
+  return sp.n_aggs >= 1;
+}
+
 /* FastHashAgg (int group key) over a table scan with the same
    keep decision, and aggregates that need a column's int or <= 38-digit
    decimal value or its presence. count(NULL) rides a column id that never
@@ -1248,6 +1281,36 @@ static copr_status translate_rpn(const CoprExecutor &ex, HostPlan *pl,
           nd.slot = s;
           nd.uns = (ci.ft.flag & COPR_FLAG_UNSIGNED) ? 1 : 0;
           if (!push(nd, +1)) return COPR_ERR_UNSUPPORTED;
+          /* col, item_1 .. item_n, IN_INT(n + 1): the items become the set
+             image and the function one kind-5 node, so the list length costs
+             neither program nodes nor stack depth */
+          uint32_t j = i + 1;
+          while (j < cond.n_nodes &&
+                 (cond.nodes[j].kind == COPR_EXPR_CONST_INT ||
+                  cond.nodes[j].kind == COPR_EXPR_CONST_UINT ||
+                  cond.nodes[j].kind == COPR_EXPR_CONST_NULL))
+            j++;
+          if (j > i + 1 && j < cond.n_nodes &&
+              cond.nodes[j].kind == COPR_EXPR_SCALAR_FUNC &&
+              cond.nodes[j].sig == COPR_SIG_IN_INT &&
+              (int64_t)cond.nodes[j].n_args == (int64_t)(j - i)) {
+            const uint32_t n_items = j - i - 1;
+            if (pl->has_in || n_items > COPR_IN_MAX_ITEMS)
+              return COPR_ERR_UNSUPPORTED;
+            std::vector<InItem> items(n_items);
+            for (uint32_t t = 0; t < n_items; t++) {
+              const CoprExprNode &it = cond.nodes[i + 1 + t];
+              items[t].bits = (uint64_t)it.i64_val;
+              items[t].uns = it.kind == COPR_EXPR_CONST_UINT ? 1 : 0;
+              items[t].null = it.kind == COPR_EXPR_CONST_NULL ? 1 : 0;
+            }
+            pl->in_set = in_set_build(items.data(), n_items, nd.uns != 0);
+            pl->has_in = true;
+            DevRpnNode in{};
+            in.kind = 5;
+            if (!push(in, 0)) return COPR_ERR_UNSUPPORTED;
+            i = j;                       /* the loop steps past the function */
+          }
           break;
         }
         case COPR_EXPR_CONST_INT:
@@ -1275,6 +1338,11 @@ static copr_status translate_rpn(const CoprExecutor &ex, HostPlan *pl,
             case COPR_SIG_INT_IS_TRUE: case COPR_SIG_INT_IS_FALSE:
               na = 1;
               break;
+            case COPR_SIG_IN_INT:
+              /* an IN the column-reference case above did not take: its
+                 probe is no column, or an item no int constant or NULL */
+              return en.n_args < 2 ? COPR_ERR_INVALID_REQUEST
+                                   : COPR_ERR_UNSUPPORTED;
             default:
               return COPR_ERR_UNSUPPORTED;
           }
@@ -1351,6 +1419,18 @@ static copr_status translate_rpn(const CoprExecutor &ex, HostPlan *pl,
   sp->rpn_on = 1;
   sp->rpn_n = n;
   for (int i = 0; i < n; i++) sp->rpn[i] = prog[i];
+  if (pl->has_in) {
+    /* the image reaches the device in copr_dag_run (in_tab), before the
+       request's timed events */
+    sp->in_mask = pl->in_set.mask;
+    sp->in_empty = pl->in_set.empty;
+    sp->in_has_null = pl->in_set.has_null ? 1 : 0;
+    const bool bare = n == 2 && prog[0].kind == 0 && prog[1].kind == 5;
+    const bool negated = n == 3 && prog[0].kind == 0 && prog[1].kind == 5 &&
+                         prog[2].kind == 3 && prog[2].sig == COPR_SIG_UNARY_NOT;
+    pl->in_simple = bare || negated;
+    pl->in_negate = negated;
+  }
   return COPR_OK;
 }
 
@@ -2278,6 +2358,25 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
   HostPlan pl;
   copr_status st = build_plan(req, &pl);
   if (st != COPR_OK) return st;
+  if (pl.has_in) {
+    /* the IN list's set image: the engine's one buffer for it
+       grows on demand (128 B .. 16 KiB). Every earlier request that read it
+       has been waited for, and hipFree waits for the device anyway. The copy
+       is on the request's stream, ahead of every launch and of the timed
+       events. */
+    const uint32_t in_slots = (uint32_t)pl.in_set.tab.size();
+    if (eng->d_in_slots < in_slots) {
+      hipFree(eng->d_in_tab);
+      eng->d_in_tab = nullptr;
+      eng->d_in_slots = 0;
+      HIP_TRY(hipMalloc(&eng->d_in_tab, (size_t)in_slots * 8), "in-set alloc");
+      eng->d_in_slots = in_slots;
+    }
+    HIP_TRY(hipMemcpyAsync(eng->d_in_tab, pl.in_set.tab.data(),
+                           pl.in_set.tab.size() * 8, hipMemcpyHostToDevice,
+                           eng->stream), "in-set upload");
+    pl.sp.in_tab = eng->d_in_tab;
+  }
 
   if (eng->dec_col_off >= 0 && !pl.has_agg && !pl.has_topn &&
       !pl.sp.has_filter && (size_t)eng->dec_col_off < pl.cols.size()) {
@@ -2672,6 +2771,43 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             nuse[rg] = NarrowUse{};
           }
       }
+      /* IN-list filter: the same wiring for k_plane_in, and for
+         a count(*) alone the filter plane's 1- or 2-byte narrow companion for
+         k_plane_inb. COPR_NO_IN_PLANES=1 (read per call) leaves the request
+         on the scan path and its kind-5 evaluator; same result bytes. */
+      const bool in_planes = !getenv("COPR_NO_PLANES") &&
+                             !getenv("COPR_NO_IN_PLANES") &&
+                             in_plane_plan_ok(pl);
+      std::vector<const DevRegion::ColPlane *> in_nar;
+      InFcArgs in_fa{};
+      uint32_t in_grid = 0;    /* diagnostic: cap the grid of both kernels */
+      if (in_planes) {
+        in_fc_fold(pl.in_set, pl.in_negate, pl.sp.filter_missing_null != 0,
+                   pl.sp.filter_missing_val, &in_fa);
+        if (const char *g = getenv("COPR_IN_GRID"))
+          in_grid = (uint32_t)strtoul(g, nullptr, 10);
+        const bool count_only = pl.sp.n_aggs == 1 &&
+                                pl.sp.aggs[0].kind == DAGG_COUNT_ROWS &&
+                                !getenv("COPR_NO_NARROW");
+        psets.resize(n_regions);
+        in_nar.assign(n_regions, nullptr);
+        for (uint32_t rg = 0; rg < n_regions; rg++) {
+          DevRegion &dev = regions[rg]->dev;
+          if (!plane_wire(eng, dev, pl.sp, &psets[rg])) {
+            psets[rg] = PlaneSet{};
+            continue;
+          }
+          if (!count_only || psets[rg].f.n_rowparse) continue;
+          uint64_t budget = dev.val_bytes / 2;       /* as plane_wire's */
+          if (const char *e = getenv("COPR_PLANE_BUDGET_MB"))
+            budget = (uint64_t)strtoull(e, nullptr, 10) << 20;
+          const DevRegion::ColPlane *np = dev_colplane_narrow(
+              dev, pl.sp.filter_col_id, budget, eng->stream,
+              &eng->narrow_builds);
+          /* a split 32-bit plane has no bitmap form: it keeps k_plane_in */
+          if (np && np->nar_w <= 2) in_nar[rg] = np;
+        }
+      }
       uint32_t fcn_grid = 0;   /* diagnostic: cap k_plane_fcn / _fcs' grid */
       if (const char *g = getenv("COPR_NARROW_GRID"))
         fcn_grid = (uint32_t)strtoul(g, nullptr, 10);
@@ -2810,6 +2946,18 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             eng->plane_launches++;
             eng->narrow_launches++;
             if (nuse[rg].p->nar_lo_off) eng->split_launches++;
+          } else if (in_planes && plane_set_used(psets[rg])) {
+            if (in_nar[rg]) {
+              e = dev_plane_inb_launch(*in_nar[rg], sp, in_fa,
+                                       regions[rg]->dev.n_kv, &d_acc[0].cnt,
+                                       in_grid, eng->stream);
+              eng->in_bitmap_launches++;
+            } else {
+              e = dev_plane_in_launch(sp, psets[rg], in_fa, regions[rg]->dev,
+                                      d_acc, in_grid, eng->stream);
+              eng->in_wide_launches++;
+            }
+            eng->plane_launches++;
           } else if (!psets.empty() && plane_set_used(psets[rg])) {
             e = dev_plane_agg_launch(sp, psets[rg], regions[rg]->dev, d_acc,
                                      eng->stream);

@@ -10,6 +10,7 @@
 
 #include "../../include/copr_types.h"   /* scalar sig / tp enums */
 #include "plane_fold.h"                  /* CMP_*, Plane/Narrow/SplitFcArgs */
+#include "in_set.h"                      /* InSet, in_set_probe, InFcArgs */
 #include "topn_keys.h"                   /* TopnKey, order-key transform, cut */
 #include "group_keys.h"                  /* GroupKey, tuple dictionary rules */
 
@@ -133,7 +134,9 @@ enum {
 struct DevRpnNode {
   int32_t kind;   /* 0 col slot, 1 const int, 2 const NULL, 3 scalar func,
                      4 gate: end of a condition that is not the last; drops
-                     the row unless the value on the stack is true */
+                     the row unless the value on the stack is true,
+                     5 IN-list membership of the value on the stack in the
+                     plan's set image: pops one, pushes one */
   int32_t sig;    /* kind 3: CoprScalarSig */
   int32_t slot;   /* kind 0: capture slot (0 = filter chan, 1 = filter2,
                      2 / 3 = extra-capture channels) */
@@ -188,6 +191,13 @@ struct ScanPlan {
   int32_t rpn_on;
   int32_t rpn_n;
   DevRpnNode rpn[COPR_MAX_RPN];
+  /* the set image of the program's kind-5 node (in_set.h), in the engine's
+     device buffer: in_mask + 1 slots of 64-bit patterns; in_has_null = the
+     list holds a NULL, so a miss is NULL and not false */
+  const unsigned long long *in_tab;
+  unsigned long long in_empty;
+  uint32_t in_mask;
+  int32_t in_has_null;
   /* RPN capture channels beyond the two filter channels (selection over
      up to 4 distinct columns, selection_executor.rs:86 ANDs any number):
      channel 2+k's value rides the capture-only pseudo-agg slot
@@ -305,6 +315,11 @@ struct PlaneSet {
   PlaneRef g;
   int32_t a_src[COPR_MAX_AGGS];
 };
+/* k_plane_agg, k_plane_hash and k_plane_in take a ScanPlan and a PlaneSet by
+   value, beside up to 128 bytes of other arguments */
+static_assert(sizeof(ScanPlan) + sizeof(PlaneSet) + 128 <= 4096,
+              "ScanPlan + PlaneSet + the other arguments of the plane kernels "
+              "must fit the 4 KiB kernel-argument segment");
 
 /* hash-agg table (device): parallel arrays.
  * keys[]: EMPTY sentinel = INT64_MIN bias — the real INT64_MIN key and the
@@ -393,6 +408,22 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
 /* simple aggregates (mode 1) over column planes instead of the row bytes */
 int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
                          const DevRegion &rgn, SimpleAggAcc *d_simple,
+                         void *stream);
+/* IN-list filter over column planes. dev_plane_in_launch:
+ * k_plane_in, the plan's aggregates over the wired planes with the keep
+ * decision one LDS probe of the plan's set image (plan.in_tab and friends).
+ * dev_plane_inb_launch: k_plane_inb, count(*) over a 1- or 2-byte narrow
+ * plane through an LDS bitmap of the keys inside the plane's range; the count
+ * is added to *d_cnt. grid_cap 0 = the default grid. */
+#define COPR_PLANE_IN_UNR 4              /* k_plane_in<1, .>: pairs per lane */
+#define COPR_PLANE_INB_UNR 4             /* k_plane_inb: 16 B loads per lane */
+int dev_plane_in_launch(const ScanPlan &plan, const PlaneSet &ps,
+                        const InFcArgs &fa, const DevRegion &rgn,
+                        SimpleAggAcc *d_simple, uint32_t grid_cap,
+                        void *stream);
+int dev_plane_inb_launch(const DevRegion::ColPlane &p, const ScanPlan &plan,
+                         const InFcArgs &fa, uint64_t n_rows,
+                         unsigned long long *d_cnt, uint32_t grid_cap,
                          void *stream);
 /* int-key hash aggregation (mode 2) over column planes; the
    plan carries table_size and lds_agg_slots as for dev_scan_launch */
@@ -589,6 +620,14 @@ struct copr_engine {
   uint32_t ht_cache_tsize = 0;
   int ht_cache_naggs = 0;
   bool ht_cache_ext = false;
+  /* the device copy of a request's IN-list set image (in_set.h):
+     d_in_slots words, grown on demand, uploaded on the stream before the
+     request's timed events, freed in engine destroy */
+  unsigned long long *d_in_tab = nullptr;
+  uint32_t d_in_slots = 0;
+  /* copr_engine_in_launches: k_plane_in / k_plane_inb launches */
+  uint64_t in_wide_launches = 0;
+  uint64_t in_bitmap_launches = 0;
   /* simple-agg accumulators ([COPR_MAX_AGGS + 1] accs, [COPR_MAX_AGGS * 2]
      high limbs): allocated on first use, re-zeroed per request with async
      memsets, freed in engine destroy */

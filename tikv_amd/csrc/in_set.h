@@ -1,0 +1,130 @@
+/* in_set.h — the set image of an int IN-list predicate: built
+ * once per request on the host, probed by the host fold and by both device
+ * sites (the RPN evaluator's kind-5 node and k_plane_in). Pure C++: no HIP,
+ * no other project header, so build and probe compile and test on their own.
+ *
+ * Semantics (TiKV compare_in_int_type_by_hash, TiDB builtinInIntSig): the
+ * probe equals an item when both denote the same integer, the probe read
+ * under the column's UNSIGNED flag and the item under its kind. The image
+ * therefore keeps only the items some probe value can equal, as 64-bit
+ * patterns: among those, integer equality is pattern equality. */
+#ifndef COPR_IN_SET_H
+#define COPR_IN_SET_H
+
+#include <stdint.h>
+#include <algorithm>
+#include <vector>
+
+namespace copr {
+
+#define COPR_IN_MAX_ITEMS 1024
+#define COPR_IN_MIN_SLOTS 16u
+#define COPR_IN_MAX_SLOTS 2048u
+
+#if defined(__HIP__) || defined(__HIPCC__)
+#define COPR_IN_HD __attribute__((host)) __attribute__((device))
+#else
+#define COPR_IN_HD
+#endif
+
+/* one list item as the request states it */
+struct InItem {
+  uint64_t bits;       /* the i64 / u64 payload */
+  uint8_t uns;         /* CONST_UINT */
+  uint8_t null;        /* CONST_NULL */
+};
+
+/* open-addressed table of tab.size() = mask + 1 slots, linear probing; a free
+   slot holds `empty`, which is no key */
+struct InSet {
+  std::vector<uint64_t> tab;
+  uint32_t mask = 0;
+  uint64_t empty = 0;
+  uint32_t n_keys = 0;
+  bool has_null = false;
+};
+
+/* multiplicative hash; the product's bits 40..50 index up to 2048 slots */
+COPR_IN_HD inline uint32_t in_set_hash(uint64_t v, uint32_t mask) {
+  return (uint32_t)((v * 0x9E3779B97F4A7C15ull) >> 40) & mask;
+}
+
+/* Is v a key? `empty` is tested first, so a probe value that equals it walks
+   to the first free slot and misses. At most half the slots are taken, so the
+   walk ends; the bound keeps a damaged image from spinning a wave. */
+COPR_IN_HD inline bool in_set_probe(const uint64_t *tab, uint32_t mask,
+                                    uint64_t empty, uint64_t v) {
+  uint32_t i = in_set_hash(v, mask);
+  for (uint32_t k = 0; k <= mask; k++) {
+    const uint64_t s = tab[i];
+    if (s == empty) return false;
+    if (s == v) return true;
+    i = (i + 1) & mask;
+  }
+  return false;
+}
+
+/* items -> image. Dropped: a negative signed item under an unsigned probe and
+   an unsigned item >= 2^63 under a signed probe (no probe value equals them),
+   and duplicates. Slots = the power of two >= 2 x keys within [16, 2048].
+   empty = the smallest of 0, 1, 2, ... that is no key: with at most 1024 keys
+   one of the first 1025 is free. n must not exceed COPR_IN_MAX_ITEMS. */
+inline InSet in_set_build(const InItem *items, size_t n, bool probe_unsigned) {
+  InSet s;
+  std::vector<uint64_t> keys;
+  keys.reserve(n);
+  for (size_t i = 0; i < n; i++) {
+    const InItem &it = items[i];
+    if (it.null) { s.has_null = true; continue; }
+    if ((it.uns != 0) != probe_unsigned && (it.bits >> 63)) continue;
+    keys.push_back(it.bits);
+  }
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  s.n_keys = (uint32_t)keys.size();
+  uint32_t slots = COPR_IN_MIN_SLOTS;
+  while (slots < 2u * s.n_keys && slots < COPR_IN_MAX_SLOTS) slots <<= 1;
+  s.mask = slots - 1;
+  /* keys are sorted: the first gap in 0, 1, 2, ... */
+  uint64_t e = 0;
+  for (uint64_t k : keys) {
+    if (k != e) break;
+    e++;
+  }
+  s.empty = e;
+  s.tab.assign(slots, e);
+  for (uint64_t k : keys) {
+    uint32_t i = in_set_hash(k, s.mask);
+    while (s.tab[i] != e) i = (i + 1) & s.mask;
+    s.tab[i] = k;
+  }
+  return s;
+}
+
+/* the node's three-valued result on a non-NULL probe, as the host fold and
+   the reference of the CPU test read it: 1 true, 0 false, -1 NULL */
+inline int in_set_eval(const InSet &s, uint64_t v) {
+  if (in_set_probe(s.tab.data(), s.mask, s.empty, v)) return 1;
+  return s.has_null ? -1 : 0;
+}
+
+/* what the plane kernels take per request (k_plane_in, k_plane_inb): keep =
+   (probe hit) != invert for an int row; never = NOT IN over a list with a
+   NULL, which keeps no row; keep_absent = the same test on the column's
+   default fill (0 when that is NULL). */
+struct InFcArgs {
+  uint32_t invert, never, keep_absent;
+};
+
+inline void in_fc_fold(const InSet &s, bool negate, bool missing_null,
+                       int64_t missing_val, InFcArgs *fa) {
+  fa->invert = negate ? 1u : 0u;
+  fa->never = (negate && s.has_null) ? 1u : 0u;
+  const bool hit = !missing_null &&
+                   in_set_probe(s.tab.data(), s.mask, s.empty,
+                                (uint64_t)missing_val);
+  fa->keep_absent = (!missing_null && !fa->never && hit != negate) ? 1u : 0u;
+}
+
+}  // namespace copr
+#endif

@@ -651,6 +651,16 @@ __device__ static inline bool d_arith_int(int32_t sig, int64_t a, int64_t b,
   return ovf;
 }
 
+/* kind-5 node: the non-NULL value's membership in the plan's set
+ * image, read from global memory (16 KiB at most, L2-resident). Out of line:
+ * the probe loop stays out of every kernel that inlines d_rpn_keep. */
+__device__ __noinline__ static bool d_in_probe_global(
+    const unsigned long long *tab, uint32_t mask, unsigned long long empty,
+    int64_t v) {
+  return in_set_probe((const uint64_t *)tab, mask, (uint64_t)empty,
+                      (uint64_t)v);
+}
+
 /* evaluate the plan's RPN predicate over the captured columns: NULL-aware
  * logical ops (impl_op.rs), comparers and arithmetic in the variant the
  * operands' UNSIGNED flags select; overflow errors the request. A gate node
@@ -706,6 +716,17 @@ __device__ static inline bool d_rpn_keep(const ScanPlan &plan,
       if (sp != 1) { *err = true; return false; }
       if (sn[0] != 0 || sv[0] == 0) return false;
       sp = 0;
+    } else if (nd.kind == 5) {
+      /* IN list: NULL probe -> NULL; a hit -> 1; a miss -> NULL when the
+         list holds a NULL, else 0 */
+      if (sp < 1 || !plan.in_tab) { *err = true; return false; }
+      if (sn[sp - 1] == 0) {
+        const bool hit = d_in_probe_global(plan.in_tab, plan.in_mask,
+                                           plan.in_empty, sv[sp - 1]);
+        sv[sp - 1] = hit ? 1 : 0;
+        sn[sp - 1] = (!hit && plan.in_has_null) ? 1 : 0;
+      }
+      su[sp - 1] = 0;
     } else {
       int na = (nd.sig == COPR_SIG_UNARY_NOT ||
                 nd.sig == COPR_SIG_INT_IS_NULL ||
@@ -2429,6 +2450,161 @@ int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
     }
   switch (plan.n_aggs) {
     case 1: CASE(1, 4); break;
+    case 2: CASE(2, 2); break;
+    case 3: CASE(3, 2); break;
+    case 4: CASE(4, 2); break;
+    default: CASE(COPR_MAX_AGGS, 1); break;
+  }
+  #undef CASE
+  return (int)hipGetLastError();
+}
+
+/* ---------------- IN-list filter over column planes ---------- */
+
+/* Simple aggregates over column planes with the keep decision
+ *   in(col, c1 .. cn)  or  not(in(col, c1 .. cn)).
+ * The host has folded the request into InFcArgs and the list into a set image
+ * (in_set.h); nothing here interprets the RPN program. At block start the 256
+ * lanes copy the image, in_mask + 1 slots of 8 B (16 KiB at most), from
+ * global memory into dynamic LDS. The block then streams exactly as
+ * k_plane_agg does: per lane 16 B of every referenced value plane (two rows)
+ * plus the two state bytes, UNR pairs in flight, every load of a step issued
+ * before the first row is looked at, grid-stride. Per row the keep decision is
+ * one LDS probe of the filter value, != invert; a NULL filter cell drops the
+ * row, an absent one takes keep_absent, never keeps nothing. REAL and ERR
+ * cells raise the parse-error flag whether or not the row is kept, and
+ * ROWPARSE rows resolve out of line (d_plane_chan). Accumulators, carry and
+ * error word are k_plane_agg's. */
+template <int NAGGS, int UNR>
+__global__ void __launch_bounds__(256)
+k_plane_in(ScanPlan plan, PlaneSet ps, InFcArgs fa,
+           const uint8_t *__restrict__ vals,
+           const uint64_t *__restrict__ val_offs, uint64_t n_rows,
+           SimpleAggAcc *__restrict__ simple_acc) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  uint64_t *s_tab = (uint64_t *)lds;
+  const uint32_t in_mask = plan.in_mask;
+  const uint64_t in_empty = plan.in_empty;
+  for (uint32_t i = threadIdx.x; i <= in_mask; i += 256u)
+    s_tab[i] = plan.in_tab[i];
+  __syncthreads();
+
+  unsigned long long l_cnt[NAGGS];
+  unsigned long long l_lo[NAGGS];
+  long long l_hi[NAGGS];
+  #pragma unroll
+  for (int a = 0; a < NAGGS; a++) { l_cnt[a] = 0; l_lo[a] = 0; l_hi[a] = 0; }
+  bool any_parse_err = false;
+  const bool invert = fa.invert != 0, never = fa.never != 0;
+  const bool keep_absent = fa.keep_absent != 0;
+
+  const uint64_t n_pairs = (n_rows + 1) >> 1;
+  const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * 256u * UNR + threadIdx.x;
+       p0 < n_pairs; p0 += step) {
+    /* all loads first (clamped, unconditional per channel), then the rows */
+    longlong2 fv[UNR], av[NAGGS][UNR];
+    uint16_t fs[UNR], ast[NAGGS][UNR];
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = min(p0 + (uint64_t)u * 256u, n_pairs - 1);
+      fv[u] = ((const longlong2 *)ps.f.val)[p];
+      fs[u] = ((const uint16_t *)ps.f.st)[p];
+      #pragma unroll
+      for (int a = 0; a < NAGGS; a++) {
+        av[a][u] = make_longlong2(0, 0); ast[a][u] = 0;
+        if (ps.a[a].val) {
+          av[a][u] = ((const longlong2 *)ps.a[a].val)[p];
+          ast[a][u] = ((const uint16_t *)ps.a[a].st)[p];
+        }
+      }
+    }
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = p0 + (uint64_t)u * 256u;
+      #pragma unroll
+      for (int h = 0; h < 2; h++) {
+        uint64_t row = p * 2 + h;
+        if (p >= n_pairs || row >= n_rows) continue;
+        ChanRes ag[NAGGS];
+        ChanRes f = d_plane_chan(ps.f, (fs[u] >> (8 * h)) & 0xFFu,
+                                 h ? fv[u].y : fv[u].x, row,
+                                 plan.filter_col_id,
+                                 plan.filter_col_unsigned != 0, 0, vals,
+                                 val_offs);
+        uint32_t fl_or = f.fl;
+        #pragma unroll
+        for (int a = 0; a < NAGGS; a++) {
+          ag[a] = ChanRes{0, 0};
+          if (ps.a[a].val)
+            ag[a] = d_plane_chan(ps.a[a], (ast[a][u] >> (8 * h)) & 0xFFu,
+                                 h ? av[a][u].y : av[a][u].x, row,
+                                 plan.aggs[a].col_id,
+                                 plan.aggs[a].col_unsigned != 0,
+                                 plan.aggs[a].kind == DAGG_COUNT_COL ? 3 : 2,
+                                 vals, val_offs);
+          fl_or |= ag[a].fl;
+        }
+        if (fl_or & CH_ERR) { any_parse_err = true; continue; }
+        bool keep;
+        if (!(f.fl & CH_FOUND)) keep = keep_absent;
+        else if (f.fl & CH_NULL) keep = false;
+        else keep = !never && in_set_probe(s_tab, in_mask, in_empty,
+                                           (uint64_t)f.v) != invert;
+        if (!keep) continue;
+        #pragma unroll
+        for (int a = 0; a < NAGGS; a++) {
+          const int32_t kind = plan.aggs[a].kind;
+          if (kind == DAGG_COUNT_ROWS) { l_cnt[a]++; continue; }
+          if ((ag[a].fl & (CH_FOUND | CH_NULL)) != CH_FOUND) continue;
+          l_cnt[a]++;
+          const int64_t v = ag[a].v;
+          if (kind == DAGG_SUM_INT) {
+            unsigned long long old = l_lo[a];
+            unsigned long long nv = old + (unsigned long long)v;
+            l_hi[a] += (nv < old ? 1 : 0) + (v < 0 ? -1 : 0);
+            l_lo[a] = nv;
+          } else if (kind == DAGG_MAX_INT || kind == DAGG_MIN_INT) {
+            unsigned long long b =
+                d_fold_xform(kind, v, plan.aggs[a].col_unsigned);
+            l_lo[a] = l_lo[a] > b ? l_lo[a] : b;
+          }
+        }
+      }
+    }
+  }
+
+  d_simple_epilogue<NAGGS>(plan, simple_acc, l_cnt, l_lo, l_hi);
+  if (any_parse_err)
+    atomicOr((unsigned int *)&simple_acc[COPR_MAX_AGGS].cnt, 1u);
+}
+
+int dev_plane_in_launch(const ScanPlan &plan, const PlaneSet &ps,
+                        const InFcArgs &fa, const DevRegion &rgn,
+                        SimpleAggAcc *d_simple, uint32_t grid_cap,
+                        void *stream) {
+  if (!rgn.n_kv) return 0;
+  if (!ps.f.val || !ps.f.st || !plan.in_tab ||
+      plan.in_mask + 1 > COPR_IN_MAX_SLOTS ||
+      (plan.in_mask & (plan.in_mask + 1)) || plan.n_aggs < 1 ||
+      plan.n_aggs > COPR_MAX_AGGS)
+    return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t n_pairs = (rgn.n_kv + 1) >> 1;
+  const uint32_t lds_bytes = (plan.in_mask + 1) * 8u;
+  /* k_plane_agg's grids: 2048 blocks = 8 per CU; the LDS image (16 KiB at
+     most) leaves that occupancy alone */
+  #define CASE(N, U)                                                         \
+    {                                                                        \
+      uint64_t nb = (n_pairs + 256u * U - 1) / (256u * U);                   \
+      const uint64_t cap = grid_cap ? grid_cap : 2048u;                      \
+      uint32_t grid = (uint32_t)(nb < cap ? nb : cap);                       \
+      hipLaunchKernelGGL((k_plane_in<N, U>), dim3(grid), dim3(256),          \
+                         lds_bytes, s, plan, ps, fa, rgn.d_vals,             \
+                         rgn.d_val_offs, rgn.n_kv, d_simple);                \
+    }
+  switch (plan.n_aggs) {
+    case 1: CASE(1, COPR_PLANE_IN_UNR); break;
     case 2: CASE(2, 2); break;
     case 3: CASE(3, 2); break;
     case 4: CASE(4, 2); break;

@@ -530,6 +530,127 @@ k_plane_fcs(const uint4 *__restrict__ hi, const uint4 *__restrict__ lo,
   fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out, stamp, t_entry, seq);
 }
 
+/* IN-list filter+count over a narrow plane of 1 or 2 bytes per row (DESIGN
+ * §9o). A stored n = v - base lies in [0, nmax], nmax < 2^(8 sizeof(T)), so
+ * the list turns into a bitmap over that domain: 32 B for one byte, 8 KiB for
+ * two. Each block zeroes its bitmap in LDS, then its lanes walk the slots of
+ * the set image (global memory, 16 KiB at most) and for every key k with
+ * (uint64)(k - base) <= nmax set bit k - base with an LDS atomic OR. The
+ * difference is taken modulo 2^64 over the 64-bit patterns, which is exact
+ * for either signedness: base + nmax does not wrap, so a key is a value of the
+ * plane exactly when the difference is at most nmax.
+ * After the barrier the block streams as k_plane_fcn does, 16 B = 16 or 8
+ * rows per lane and load, UNR loads in flight, loads clamped to the last
+ * vector and rows masked by n_rows. The row test is one LDS word read and a
+ * shift, != invert; a byte of the tail slack indexes inside the bitmap
+ * whatever it holds. Every row is a known int: no state, no ABSENT fill, no
+ * parse error. Counts reduce through LDS and the block adds once to
+ * *cnt_out, the request's ordinary accumulator. */
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_plane_inb(const uint4 *__restrict__ data, uint64_t n_rows,
+            const unsigned long long *__restrict__ tab, uint32_t n_slots,
+            unsigned long long empty, unsigned long long base,
+            unsigned long long nmax, uint32_t invert, uint32_t never,
+            unsigned long long *__restrict__ cnt_out) {
+  constexpr int UNR = COPR_PLANE_INB_UNR;
+  constexpr uint32_t R = 16u / sizeof(T);          /* rows per 16 B */
+  constexpr uint32_t PW = 4u / sizeof(T);          /* rows per 32-bit word */
+  constexpr uint32_t BITS = 1u << (8 * sizeof(T));
+  constexpr uint32_t WORDS = BITS / 32u;
+  __shared__ uint32_t s_bm[WORDS];
+  __shared__ unsigned long long s_cnt[4];
+  for (uint32_t i = threadIdx.x; i < WORDS; i += 256u) s_bm[i] = 0;
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n_slots; i += 256u) {
+    const unsigned long long k = tab[i];
+    const unsigned long long d = k - base;
+    if (k != empty && d <= nmax && d < BITS)
+      atomicOr(&s_bm[(uint32_t)d >> 5], 1u << ((uint32_t)d & 31u));
+  }
+  __syncthreads();
+
+  const bool inv = invert != 0;
+  unsigned long long cnt = 0;
+  const uint64_t n_vec = (n_rows + R - 1) / R;
+  const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
+  for (uint64_t p0 = (uint64_t)blockIdx.x * 256u * UNR + threadIdx.x;
+       p0 < n_vec; p0 += step) {
+    uint4 v[UNR];
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      uint64_t p = min(p0 + (uint64_t)u * 256u, n_vec - 1);
+      v[u] = data[p];
+    }
+    /* all four loads issue before the first is used */
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t c = 0;
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      const uint64_t p = p0 + (uint64_t)u * 256u;
+      /* rows of this vector inside the plane: R except in the last vector */
+      uint32_t live = 0;
+      if (p < n_vec) {
+        const uint64_t left = n_rows - p * R;
+        live = left < R ? (uint32_t)left : R;
+      }
+      const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+      #pragma unroll
+      for (uint32_t j = 0; j < R; j++) {
+        const uint32_t n =
+            (w[j / PW] >> (8u * sizeof(T) * (j % PW))) & (BITS - 1u);
+        const bool in = ((s_bm[n >> 5] >> (n & 31u)) & 1u) != 0;
+        c += (j < live && in != inv) ? 1u : 0u;
+      }
+    }
+    cnt += c;
+  }
+  if (never) cnt = 0;
+
+  for (int off = 32; off > 0; off >>= 1)
+    cnt += (unsigned long long)__shfl_down((long long)cnt, off, 64);
+  if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long b = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    if (b) atomicAdd(cnt_out, b);
+  }
+}
+
+int dev_plane_inb_launch(const DevRegion::ColPlane &p, const ScanPlan &plan,
+                         const InFcArgs &fa, uint64_t n_rows,
+                         unsigned long long *d_cnt, uint32_t grid_cap,
+                         void *stream) {
+  if (!n_rows) return 0;
+  if (!p.nar || (p.nar_w != 1 && p.nar_w != 2) || p.nar_lo_off ||
+      p.nar_nmax >= (1ull << (8 * p.nar_w)) || !plan.in_tab ||
+      plan.in_mask + 1 > COPR_IN_MAX_SLOTS ||
+      (plan.in_mask & (plan.in_mask + 1)))
+    return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t rows_per_vec = 16u / p.nar_w;
+  const uint64_t n_vec = (n_rows + rows_per_vec - 1) / rows_per_vec;
+  /* k_plane_fcn's grid: 2048 blocks = 8 per CU */
+  uint64_t nb = (n_vec + 256u * COPR_PLANE_INB_UNR - 1) /
+                (256u * COPR_PLANE_INB_UNR);
+  const uint64_t cap = grid_cap ? grid_cap : 2048u;
+  if (nb > cap) nb = cap;
+  const uint4 *data = (const uint4 *)p.nar;
+  if (p.nar_w == 1)
+    hipLaunchKernelGGL(k_plane_inb<uint8_t>, dim3((uint32_t)nb), dim3(256), 0,
+                       s, data, n_rows, plan.in_tab, plan.in_mask + 1,
+                       plan.in_empty, (unsigned long long)p.nar_base,
+                       (unsigned long long)p.nar_nmax, fa.invert, fa.never,
+                       d_cnt);
+  else
+    hipLaunchKernelGGL(k_plane_inb<uint16_t>, dim3((uint32_t)nb), dim3(256), 0,
+                       s, data, n_rows, plan.in_tab, plan.in_mask + 1,
+                       plan.in_empty, (unsigned long long)p.nar_base,
+                       (unsigned long long)p.nar_nmax, fa.invert, fa.never,
+                       d_cnt);
+  return (int)hipGetLastError();
+}
+
 int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
                          const SplitFcArgs &sf, uint64_t n_rows,
                          unsigned long long *d_cnt,

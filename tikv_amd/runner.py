@@ -297,6 +297,22 @@ def cmp_col_const(offset, sig, const, unsigned_const=False):
     return Expr().col(offset).const_int(const, unsigned_const).func(sig, 2)
 
 
+def in_col_consts(offset, items, negate=False):
+    """col IN (items) as one condition: `items` holds Python ints, None for
+    NULL, or (int, True) for an unsigned constant; 1 to 1024 of them
+    (DESIGN.md §9o). negate=True wraps the node in UNARY_NOT: NOT IN."""
+    e = Expr().col(offset)
+    for it in items:
+        if it is None:
+            e.const_null()
+        elif isinstance(it, tuple):
+            e.const_int(it[0], unsigned=bool(it[1]))
+        else:
+            e.const_int(it)
+    e.func(F.SIG_IN_INT, len(items) + 1)
+    return e.func(F.SIG_UNARY_NOT, 1) if negate else e
+
+
 class GenRegion:
     """Synthetic region (host buffers from the product generator)."""
 
@@ -582,6 +598,15 @@ class Engine:
         since the engine was created. Other branches move neither."""
         return (self._lib.copr_engine_fc_polled(self._h),
                 self._lib.copr_engine_fc_fallbacks(self._h))
+
+    def in_stats(self):
+        """(wide launches, bitmap launches): per-region launches of the
+        IN-list kernels, k_plane_in over the wide planes and k_plane_inb over
+        a 1- or 2-byte narrow plane (plane_stats()[0] counts both too), since
+        the engine was created."""
+        w, b = C.c_uint64(), C.c_uint64()
+        self._lib.copr_engine_in_launches(self._h, C.byref(w), C.byref(b))
+        return w.value, b.value
 
     def topn_stats(self):
         """(runs, kept, candidates): TopN requests served by the multi-key
