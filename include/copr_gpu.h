@@ -123,6 +123,9 @@ uint64_t    copr_engine_fc_fallbacks(const copr_engine *);
  * both too). Monotonic. */
 void        copr_engine_in_launches(const copr_engine *, uint64_t *wide,
                                     uint64_t *bitmap);
+/* and of the IN-list filter+count kernel over a split plane;
+ * copr_engine_plane_launches counts them, copr_engine_in_launches does not */
+uint64_t    copr_engine_in_split_launches(const copr_engine *);
 /* TopN over several order-by columns: requests served by the
  * multi-key pipeline (monotonic), and for the last of them the rows its
  * filters kept (m) and the rows that passed the primary-key candidate cut

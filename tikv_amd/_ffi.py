@@ -178,6 +178,8 @@ def load_lib():
     lib.copr_engine_in_launches.restype = None
     lib.copr_engine_in_launches.argtypes = [C.c_void_p, C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint64)]
+    lib.copr_engine_in_split_launches.restype = C.c_uint64
+    lib.copr_engine_in_split_launches.argtypes = [C.c_void_p]
     lib.copr_engine_topn_multi_runs.restype = C.c_uint64
     lib.copr_engine_topn_multi_runs.argtypes = [C.c_void_p]
     lib.copr_engine_topn_last_kept.restype = C.c_uint64

@@ -118,6 +118,10 @@ extern "C" void copr_engine_in_launches(const copr_engine *eng, uint64_t *wide,
   if (bitmap) *bitmap = eng ? eng->in_bitmap_launches : 0;
 }
 
+extern "C" uint64_t copr_engine_in_split_launches(const copr_engine *eng) {
+  return eng ? eng->in_split_launches : 0;
+}
+
 extern "C" uint64_t copr_engine_fc_polled(const copr_engine *eng) {
   return eng ? eng->fc_polled : 0;
 }
@@ -2771,16 +2775,19 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             nuse[rg] = NarrowUse{};
           }
       }
-      /* IN-list filter: the same wiring for k_plane_in, and for
-         a count(*) alone the filter plane's 1- or 2-byte narrow companion for
-         k_plane_inb. COPR_NO_IN_PLANES=1 (read per call) leaves the request
-         on the scan path and its kind-5 evaluator; same result bytes. */
+      /* IN-list filter: the same wiring for k_plane_in, and
+         for a count(*) alone the filter plane's narrow companion: k_plane_inb
+         over 1 or 2 bytes per row, k_plane_ins over a split plane.
+         COPR_NO_IN_PLANES=1 (read per call) leaves the request on the scan
+         path and its kind-5 evaluator, COPR_NO_IN_SPLIT=1 (read per call)
+         leaves a split plane's region on k_plane_in; same result bytes. */
       const bool in_planes = !getenv("COPR_NO_PLANES") &&
                              !getenv("COPR_NO_IN_PLANES") &&
                              in_plane_plan_ok(pl);
       std::vector<const DevRegion::ColPlane *> in_nar;
+      std::vector<InSplitArgs> in_sa;
       InFcArgs in_fa{};
-      uint32_t in_grid = 0;    /* diagnostic: cap the grid of both kernels */
+      uint32_t in_grid = 0;    /* diagnostic: cap the grid of the IN kernels */
       if (in_planes) {
         in_fc_fold(pl.in_set, pl.in_negate, pl.sp.filter_missing_null != 0,
                    pl.sp.filter_missing_val, &in_fa);
@@ -2789,8 +2796,10 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         const bool count_only = pl.sp.n_aggs == 1 &&
                                 pl.sp.aggs[0].kind == DAGG_COUNT_ROWS &&
                                 !getenv("COPR_NO_NARROW");
+        const bool in_split = !getenv("COPR_NO_IN_SPLIT");
         psets.resize(n_regions);
         in_nar.assign(n_regions, nullptr);
+        in_sa.assign(n_regions, InSplitArgs{});
         for (uint32_t rg = 0; rg < n_regions; rg++) {
           DevRegion &dev = regions[rg]->dev;
           if (!plane_wire(eng, dev, pl.sp, &psets[rg])) {
@@ -2804,10 +2813,36 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
           const DevRegion::ColPlane *np = dev_colplane_narrow(
               dev, pl.sp.filter_col_id, budget, eng->stream,
               &eng->narrow_builds);
-          /* a split 32-bit plane has no bitmap form: it keeps k_plane_in */
-          if (np && np->nar_w <= 2) in_nar[rg] = np;
+          if (!np) continue;
+          if (np->nar_w <= 2) {
+            in_nar[rg] = np;
+          } else if (in_split) {
+            /* a split plane has no bitmap of values: one of buckets */
+            in_nar[rg] = np;
+            in_split_fold(pl.in_set, np->nar_base, np->nar_nmax, &in_sa[rg]);
+          }
         }
       }
+      /* an IN request finishes in one dispatch under the range request's
+         rule: every region on a narrow plane */
+      bool in_one = in_planes && n_regions > 0;
+      for (uint32_t rg = 0; in_one && rg < n_regions; rg++)
+        if (!in_nar[rg]) in_one = false;
+      /* one launch of an IN request over a narrow plane; its counters */
+      auto in_narrow_launch = [&](uint32_t rg, unsigned long long *d_cnt,
+                                  uint32_t n_slots, unsigned int *d_ticket,
+                                  unsigned long long *h_out,
+                                  unsigned long long *d_stamp,
+                                  unsigned long long seq) -> int {
+        const int e = dev_plane_inn_launch(*in_nar[rg], pl.sp, in_fa, in_sa[rg],
+                                           regions[rg]->dev.n_kv, d_cnt,
+                                           n_slots, d_ticket, h_out, d_stamp,
+                                           seq, in_grid, eng->stream);
+        eng->plane_launches++;
+        if (in_nar[rg]->nar_lo_off) eng->in_split_launches++;
+        else eng->in_bitmap_launches++;
+        return e;
+      };
       uint32_t fcn_grid = 0;   /* diagnostic: cap k_plane_fcn / _fcs' grid */
       if (const char *g = getenv("COPR_NARROW_GRID"))
         fcn_grid = (uint32_t)strtoul(g, nullptr, 10);
@@ -2816,9 +2851,9 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
          the whole result is one count, which the last launch's last block
          hands to the pinned host word while it re-zeroes the device words.
          No memset and no copy in the steady state. */
-      bool one_dispatch = n_regions > 0 && !nuse.empty() &&
+      bool one_dispatch = n_regions > 0 && (in_one || !nuse.empty()) &&
                           !getenv("COPR_NARROW_NO_FINALIZE");
-      for (uint32_t rg = 0; one_dispatch && rg < n_regions; rg++)
+      for (uint32_t rg = 0; one_dispatch && !in_one && rg < n_regions; rg++)
         if (!nuse[rg].p) one_dispatch = false;
       if (one_dispatch && !eng->d_fcn_state) {
         /* first use; on failure the request takes the usual sequence */
@@ -2873,21 +2908,30 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         uint64_t stream_bytes = 0;
         for (uint32_t rg = 0; rg < n_regions; rg++) {
           const bool last = rg + 1 == n_regions;
-          int e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf, nuse[rg].sf,
-                                       regions[rg]->dev.n_kv, d_cnt,
-                                       COPR_FCN_SLOTS,
-                                       last ? d_ticket : nullptr,
-                                       last ? eng->h_fcn_out : nullptr,
-                                       rg == 0 ? d_stamp : nullptr, seq,
-                                       fcn_grid, eng->stream);
-          eng->plane_launches++;
-          eng->narrow_launches++;
-          if (nuse[rg].p->nar_lo_off) eng->split_launches++;
+          int e;
+          if (in_one) {
+            e = in_narrow_launch(rg, d_cnt, COPR_FCN_SLOTS,
+                                 last ? d_ticket : nullptr,
+                                 last ? eng->h_fcn_out : nullptr,
+                                 rg == 0 ? d_stamp : nullptr, seq);
+            stream_bytes += regions[rg]->dev.n_kv * in_nar[rg]->nar_w;
+          } else {
+            e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf, nuse[rg].sf,
+                                     regions[rg]->dev.n_kv, d_cnt,
+                                     COPR_FCN_SLOTS,
+                                     last ? d_ticket : nullptr,
+                                     last ? eng->h_fcn_out : nullptr,
+                                     rg == 0 ? d_stamp : nullptr, seq,
+                                     fcn_grid, eng->stream);
+            eng->plane_launches++;
+            eng->narrow_launches++;
+            if (nuse[rg].p->nar_lo_off) eng->split_launches++;
+            stream_bytes += regions[rg]->dev.n_kv * nuse[rg].p->nar_w;
+          }
           if (e) {
             eng->fcn_dirty = true;
             return SET_ERR(COPR_ERR_INTERNAL, "narrow plane launch failed");
           }
-          stream_bytes += regions[rg]->dev.n_kv * nuse[rg].p->nar_w;
         }
         /* How long to spin before handing the wait to the runtime: the bytes
            the launches can read (a split plane's both halves) at 50 GB/s, a
@@ -2948,16 +2992,15 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             if (nuse[rg].p->nar_lo_off) eng->split_launches++;
           } else if (in_planes && plane_set_used(psets[rg])) {
             if (in_nar[rg]) {
-              e = dev_plane_inb_launch(*in_nar[rg], sp, in_fa,
-                                       regions[rg]->dev.n_kv, &d_acc[0].cnt,
-                                       in_grid, eng->stream);
-              eng->in_bitmap_launches++;
+              /* one slot, no ticket: the count joins the other regions' */
+              e = in_narrow_launch(rg, &d_acc[0].cnt, 1, nullptr, nullptr,
+                                   nullptr, 0);
             } else {
               e = dev_plane_in_launch(sp, psets[rg], in_fa, regions[rg]->dev,
                                       d_acc, in_grid, eng->stream);
               eng->in_wide_launches++;
+              eng->plane_launches++;
             }
-            eng->plane_launches++;
           } else if (!psets.empty() && plane_set_used(psets[rg])) {
             e = dev_plane_agg_launch(sp, psets[rg], regions[rg]->dev, d_acc,
                                      eng->stream);

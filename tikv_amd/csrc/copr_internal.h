@@ -412,19 +412,27 @@ int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
 /* IN-list filter over column planes. dev_plane_in_launch:
  * k_plane_in, the plan's aggregates over the wired planes with the keep
  * decision one LDS probe of the plan's set image (plan.in_tab and friends).
- * dev_plane_inb_launch: k_plane_inb, count(*) over a 1- or 2-byte narrow
- * plane through an LDS bitmap of the keys inside the plane's range; the count
- * is added to *d_cnt. grid_cap 0 = the default grid. */
+ * dev_plane_inn_launch: count(*) over the filter plane's narrow companion,
+ * by its width: k_plane_inb over 1 or 2 bytes per row, through an LDS bitmap
+ * of the keys inside the plane's range, and k_plane_ins over a split plane
+ * (sa from in_split_fold, unused otherwise). The count goes to
+ * n_slots count words at d_cnt, and d_ticket, h_out, d_stamp and seq finalize
+ * a one-dispatch request, all exactly as for dev_plane_fcn_launch. grid_cap
+ * 0 = the default grid. */
 #define COPR_PLANE_IN_UNR 4              /* k_plane_in<1, .>: pairs per lane */
-#define COPR_PLANE_INB_UNR 4             /* k_plane_inb: 16 B loads per lane */
+#define COPR_PLANE_INB_UNR 4             /* k_plane_inb / _ins: loads per lane */
+#define COPR_PLANE_INS_BM_WORDS 2048     /* k_plane_ins: one bit per bucket */
 int dev_plane_in_launch(const ScanPlan &plan, const PlaneSet &ps,
                         const InFcArgs &fa, const DevRegion &rgn,
                         SimpleAggAcc *d_simple, uint32_t grid_cap,
                         void *stream);
-int dev_plane_inb_launch(const DevRegion::ColPlane &p, const ScanPlan &plan,
-                         const InFcArgs &fa, uint64_t n_rows,
-                         unsigned long long *d_cnt, uint32_t grid_cap,
-                         void *stream);
+int dev_plane_inn_launch(const DevRegion::ColPlane &p, const ScanPlan &plan,
+                         const InFcArgs &fa, const InSplitArgs &sa,
+                         uint64_t n_rows, unsigned long long *d_cnt,
+                         uint32_t n_slots, unsigned int *d_ticket,
+                         unsigned long long *h_out,
+                         unsigned long long *d_stamp, unsigned long long seq,
+                         uint32_t grid_cap, void *stream);
 /* int-key hash aggregation (mode 2) over column planes; the
    plan carries table_size and lds_agg_slots as for dev_scan_launch */
 int dev_plane_hash_launch(const ScanPlan &plan, const PlaneSet &ps,
@@ -628,6 +636,8 @@ struct copr_engine {
   /* copr_engine_in_launches: k_plane_in / k_plane_inb launches */
   uint64_t in_wide_launches = 0;
   uint64_t in_bitmap_launches = 0;
+  /* copr_engine_in_split_launches: k_plane_ins launches */
+  uint64_t in_split_launches = 0;
   /* simple-agg accumulators ([COPR_MAX_AGGS + 1] accs, [COPR_MAX_AGGS * 2]
      high limbs): allocated on first use, re-zeroed per request with async
      memsets, freed in engine destroy */

@@ -126,5 +126,71 @@ inline void in_fc_fold(const InSet &s, bool negate, bool missing_null,
   fa->keep_absent = (!missing_null && !fa->never && hit != negate) ? 1u : 0u;
 }
 
+/* ---- the list over a split 32-bit plane (k_plane_ins) --------
+ * The plane stores n = v - base in [0, nmax], nmax < 2^32, as h = n >> 16 and
+ * l = n & 0xFFFF. A key k is a value of the plane exactly when d = k - base,
+ * taken modulo 2^64 over the patterns as in k_plane_inb, is <= nmax (base +
+ * nmax does not wrap, for either signedness); its bucket is d >> 16. A row
+ * whose h names no flagged bucket cannot hit, whatever its l. */
+COPR_IN_HD inline bool in_split_bucket(uint64_t k, uint64_t empty,
+                                       uint64_t base, uint64_t nmax,
+                                       uint32_t *bucket) {
+  const uint64_t d = k - base;
+  if (k == empty || d > nmax || d > 0xFFFFFFFFull) return false;
+  *bucket = (uint32_t)(d >> 16);
+  return true;
+}
+
+/* the hull [hull_lo, hull_lo + hull_span] of the flagged buckets, also in the
+   packed 16-bit form of DESIGN §9l (the value in both halves of a word, for
+   packed_out_acc); none = no key lies in the plane's domain, the hull is then
+   unused (zero). flagged = how many buckets hold a key, of buckets = (nmax >>
+   16) + 1: the share of a uniform plane's rows that reach the probe. */
+struct InSplitArgs {
+  uint32_t hull_lo, hull_span;
+  uint32_t hull_lo_pk, hull_span_pk;
+  uint32_t none;
+  uint32_t flagged, buckets;
+};
+
+/* image + plane domain -> InSplitArgs and, when bm is given, the bucket bitmap
+   the kernel builds in LDS: (nmax >> 21) + 1 words */
+inline void in_split_fold(const InSet &s, int64_t base, uint64_t nmax,
+                          InSplitArgs *a, std::vector<uint32_t> *bm = nullptr) {
+  uint32_t lo = 0xFFFFFFFFu, hi = 0;
+  std::vector<uint32_t> own;
+  if (!bm) bm = &own;
+  bm->assign((size_t)(nmax >> 21) + 1, 0u);
+  a->flagged = 0;
+  a->buckets = (uint32_t)(nmax >> 16) + 1u;
+  for (uint64_t k : s.tab) {
+    uint32_t b;
+    if (!in_split_bucket(k, s.empty, (uint64_t)base, nmax, &b)) continue;
+    lo = b < lo ? b : lo;
+    hi = b > hi ? b : hi;
+    if (!(((*bm)[b >> 5] >> (b & 31u)) & 1u)) a->flagged++;
+    (*bm)[b >> 5] |= 1u << (b & 31u);
+  }
+  a->none = lo > hi ? 1u : 0u;
+  a->hull_lo = a->none ? 0u : lo;
+  a->hull_span = a->none ? 0u : hi - lo;
+  a->hull_lo_pk = a->hull_lo * 0x10001u;
+  a->hull_span_pk = a->hull_span * 0x10001u;
+}
+
+/* the row rule: a clear bucket bit misses; a set one probes the image with
+   the row's full value; keep = hit != invert, and never keeps nothing. h must
+   not exceed nmax >> 16 (every row of the plane obeys). */
+COPR_IN_HD inline bool in_split_row(uint32_t h, uint32_t l, const uint32_t *bm,
+                                    const uint64_t *tab, uint32_t mask,
+                                    uint64_t empty, uint64_t base,
+                                    uint32_t invert, uint32_t never) {
+  if (never) return false;
+  bool hit = false;
+  if ((bm[h >> 5] >> (h & 31u)) & 1u)
+    hit = in_set_probe(tab, mask, empty, base + (((uint64_t)h << 16) | l));
+  return hit != (invert != 0);
+}
+
 }  // namespace copr
 #endif

@@ -544,22 +544,25 @@ k_plane_fcs(const uint4 *__restrict__ hi, const uint4 *__restrict__ lo,
  * vector and rows masked by n_rows. The row test is one LDS word read and a
  * shift, != invert; a byte of the tail slack indexes inside the bitmap
  * whatever it holds. Every row is a known int: no state, no ABSENT fill, no
- * parse error. Counts reduce through LDS and the block adds once to
- * *cnt_out, the request's ordinary accumulator. */
+ * parse error. The tail is fcn_block_count's: count slots, and
+ * with a ticket the launch finalizes its request as k_plane_fcn does. */
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_plane_inb(const uint4 *__restrict__ data, uint64_t n_rows,
             const unsigned long long *__restrict__ tab, uint32_t n_slots,
             unsigned long long empty, unsigned long long base,
             unsigned long long nmax, uint32_t invert, uint32_t never,
-            unsigned long long *__restrict__ cnt_out) {
+            unsigned long long *__restrict__ cnt_out, uint32_t slot_mask,
+            unsigned int *__restrict__ ticket,
+            unsigned long long *__restrict__ h_out,
+            unsigned long long *__restrict__ stamp, unsigned long long seq) {
+  const unsigned long long t_entry = fcn_entry_clock(stamp);
   constexpr int UNR = COPR_PLANE_INB_UNR;
   constexpr uint32_t R = 16u / sizeof(T);          /* rows per 16 B */
   constexpr uint32_t PW = 4u / sizeof(T);          /* rows per 32-bit word */
   constexpr uint32_t BITS = 1u << (8 * sizeof(T));
   constexpr uint32_t WORDS = BITS / 32u;
   __shared__ uint32_t s_bm[WORDS];
-  __shared__ unsigned long long s_cnt[4];
   for (uint32_t i = threadIdx.x; i < WORDS; i += 256u) s_bm[i] = 0;
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < n_slots; i += 256u) {
@@ -606,48 +609,222 @@ k_plane_inb(const uint4 *__restrict__ data, uint64_t n_rows,
     cnt += c;
   }
   if (never) cnt = 0;
-
-  for (int off = 32; off > 0; off >>= 1)
-    cnt += (unsigned long long)__shfl_down((long long)cnt, off, 64);
-  if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long b = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    if (b) atomicAdd(cnt_out, b);
-  }
+  fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out, stamp, t_entry, seq);
 }
 
-int dev_plane_inb_launch(const DevRegion::ColPlane &p, const ScanPlan &plan,
-                         const InFcArgs &fa, uint64_t n_rows,
-                         unsigned long long *d_cnt, uint32_t grid_cap,
-                         void *stream) {
-  if (!n_rows) return 0;
-  if (!p.nar || (p.nar_w != 1 && p.nar_w != 2) || p.nar_lo_off ||
+/* IN-list filter+count over a split plane: k_plane_fcs's shape
+ * with the list in the place of the range. A key can only equal a row whose
+ * high half names the key's bucket (in_set.h, in_split_bucket), so the high
+ * halves alone dismiss every row outside the flagged buckets.
+ * Prologue, once per block: zero the bucket bitmap's words up to nmax >> 16
+ * (8 KiB at most), then walk the image's slots, copy each to the LDS image
+ * (dynamic, n_slots x 8 B, 16 KiB at most) and set its key's bucket bit with
+ * an LDS atomic OR; one barrier.
+ * Phase one reads 16 B = 8 rows of hi per lane and load, four loads in flight.
+ * An iteration fully inside the plane counts its rows packed over the hull of
+ * the flagged buckets (sa.hull_*_pk, two rows per instruction); a wave whose
+ * ballot finds every row outside the hull reads no LDS. Otherwise each row's h
+ * is tested against the bitmap, one LDS word and a shift: amb = the live rows
+ * whose bucket is flagged. A row at or beyond n_rows is never open; the tail
+ * slack may hold an h beyond the zeroed words, still inside the array.
+ * Phase two is k_plane_fcs's: a wave-uniform ballot on amb, predicated lo
+ * loads per vector in a sparse wave and unpredicated ones with 16 or more open
+ * lanes, all before first use; each open row probes the LDS image with
+ * base + ((h << 16) | l).
+ * A launch with sa.none or never streams nothing (the launcher gives it one
+ * block): NOT IN without a key in the domain keeps every row, the other forms
+ * none. It still passes through the tail, so a one-dispatch request ends. */
+__global__ void __launch_bounds__(256)
+k_plane_ins(const uint4 *__restrict__ hi, const uint4 *__restrict__ lo,
+            uint64_t n_rows, const unsigned long long *__restrict__ tab,
+            uint32_t n_slots, unsigned long long empty,
+            unsigned long long base, unsigned long long nmax, InSplitArgs sa,
+            uint32_t invert, uint32_t never,
+            unsigned long long *__restrict__ cnt_out, uint32_t slot_mask,
+            unsigned int *__restrict__ ticket,
+            unsigned long long *__restrict__ h_out,
+            unsigned long long *__restrict__ stamp, unsigned long long seq) {
+  const unsigned long long t_entry = fcn_entry_clock(stamp);
+  constexpr int UNR = 4;
+  constexpr uint32_t R = 8;                        /* rows per 16 B */
+  __shared__ uint32_t s_bm[COPR_PLANE_INS_BM_WORDS];
+  extern __shared__ uint64_t s_tab[];
+  const bool inv = invert != 0;
+  unsigned long long cnt = 0;
+  /* kernel-uniform */
+  const bool streams = !sa.none && !never;
+  if (!streams) {
+    if (inv && !never && blockIdx.x == 0 && threadIdx.x == 0) cnt = n_rows;
+  } else {
+    uint32_t bm_words = ((uint32_t)(nmax >> 16) >> 5) + 1u;
+    if (bm_words > COPR_PLANE_INS_BM_WORDS) bm_words = COPR_PLANE_INS_BM_WORDS;
+    for (uint32_t i = threadIdx.x; i < bm_words; i += 256u) s_bm[i] = 0;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n_slots; i += 256u) {
+      const uint64_t k = tab[i];
+      s_tab[i] = k;
+      uint32_t b;
+      if (in_split_bucket(k, empty, base, nmax, &b))
+        atomicOr(&s_bm[b >> 5], 1u << (b & 31u));
+    }
+    __syncthreads();
+  }
+  const uint32_t in_mask = n_slots - 1u;
+  const uint64_t n_vec = streams ? (n_rows + R - 1) / R : 0;
+  const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
+  /* b0 = p0 - threadIdx.x, the block's first vector, kept beside p0 so that
+     the compiler sees it is the same in every lane */
+  uint64_t b0 = (uint64_t)blockIdx.x * 256u * UNR;
+  for (uint64_t p0 = b0 + threadIdx.x; p0 < n_vec; p0 += step, b0 += step) {
+    uint4 v[UNR];
+    /* one bit per row, vector u in bits 8u .. 8u + 7 */
+    uint32_t livem = ~0u, amb = 0;
+    bool classify = true;
+    if ((b0 + 256u * UNR) * R <= n_rows) {
+      #pragma unroll
+      for (int u = 0; u < UNR; u++) v[u] = hi[p0 + (uint64_t)u * 256u];
+      /* all four loads issue before the first is used */
+      __builtin_amdgcn_sched_barrier(0);
+      uint32_t acc = 0;
+      #pragma unroll
+      for (int u = 0; u < UNR; u++)
+        acc = packed_out_acc(v[u], sa.hull_lo_pk, sa.hull_span_pk, acc);
+      /* rows outside the hull; a wave with none inside it is done */
+      classify =
+          __builtin_amdgcn_ballot_w64(packed_sum(acc) != UNR * R) != 0;
+    } else {
+      #pragma unroll
+      for (int u = 0; u < UNR; u++) {
+        uint64_t p = min(p0 + (uint64_t)u * 256u, n_vec - 1);
+        v[u] = hi[p];
+      }
+      /* all four loads issue before the first is used */
+      __builtin_amdgcn_sched_barrier(0);
+      livem = 0;
+      #pragma unroll
+      for (int u = 0; u < UNR; u++) {
+        const uint64_t p = p0 + (uint64_t)u * 256u;
+        uint32_t live = 0;
+        if (p < n_vec) {
+          const uint64_t left = n_rows - p * R;
+          live = left < R ? (uint32_t)left : R;
+        }
+        livem |= ((1u << live) - 1u) << (u * R);
+      }
+    }
+    if (classify) {             /* wave-uniform */
+      #pragma unroll
+      for (int u = 0; u < UNR; u++) {
+        const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+        #pragma unroll
+        for (uint32_t j = 0; j < R; j++) {
+          const uint32_t h = (j & 1u) ? w[j / 2] >> 16 : w[j / 2] & 0xFFFFu;
+          amb |= ((s_bm[h >> 5] >> (h & 31u)) & 1u) << (u * R + j);
+        }
+      }
+      amb &= livem;
+    }
+    uint32_t in = 0;
+    const unsigned long long open_lanes =
+        __builtin_amdgcn_ballot_w64(amb != 0);
+    if (open_lanes != 0) {
+      uint4 lv[UNR];
+      if (__popcll(open_lanes) >= 16) {
+        /* dense (wave-uniform): every lane loads its four vectors,
+           unpredicated and coalesced */
+        #pragma unroll
+        for (int u = 0; u < UNR; u++)
+          lv[u] = lo[min(p0 + (uint64_t)u * 256u, n_vec - 1)];
+      } else {
+        #pragma unroll
+        for (int u = 0; u < UNR; u++) {
+          lv[u] = make_uint4(0, 0, 0, 0);
+          if ((amb >> (u * R)) & 0xFFu)
+            lv[u] = lo[min(p0 + (uint64_t)u * 256u, n_vec - 1)];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      #pragma unroll
+      for (int u = 0; u < UNR; u++) {
+        if (!((amb >> (u * R)) & 0xFFu)) continue;
+        const uint32_t wh[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+        const uint32_t wl[4] = {lv[u].x, lv[u].y, lv[u].z, lv[u].w};
+        #pragma unroll
+        for (uint32_t j = 0; j < R; j++) {
+          if (!((amb >> (u * R + j)) & 1u)) continue;
+          const uint32_t h = (j & 1u) ? wh[j / 2] >> 16 : wh[j / 2] & 0xFFFFu;
+          const uint32_t l = (j & 1u) ? wl[j / 2] >> 16 : wl[j / 2] & 0xFFFFu;
+          in += in_set_probe(s_tab, in_mask, empty,
+                             base + (((uint64_t)h << 16) | l)) ? 1u : 0u;
+        }
+      }
+    }
+    cnt += inv ? __popc(livem) - in : in;
+  }
+  fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out, stamp, t_entry, seq);
+}
+
+int dev_plane_inn_launch(const DevRegion::ColPlane &p, const ScanPlan &plan,
+                         const InFcArgs &fa, const InSplitArgs &sa,
+                         uint64_t n_rows, unsigned long long *d_cnt,
+                         uint32_t n_slots, unsigned int *d_ticket,
+                         unsigned long long *h_out,
+                         unsigned long long *d_stamp, unsigned long long seq,
+                         uint32_t grid_cap, void *stream) {
+  /* dev_plane_fcn_launch's checks on the one-dispatch arguments */
+  if (d_stamp && d_ticket &&
+      d_stamp != (unsigned long long *)d_ticket + COPR_FCN_STAMP_WORD)
+    return -1;
+  if (!p.nar || (d_ticket && (!h_out || !seq)) || !n_slots || n_slots > 64 ||
+      (n_slots & (n_slots - 1)) || (p.nar_w == 4) != (p.nar_lo_off != 0))
+    return -1;
+  /* and k_plane_inb's on the plane and the image */
+  if ((p.nar_w != 1 && p.nar_w != 2 && p.nar_w != 4) ||
       p.nar_nmax >= (1ull << (8 * p.nar_w)) || !plan.in_tab ||
+      plan.in_mask + 1 < COPR_IN_MIN_SLOTS ||
       plan.in_mask + 1 > COPR_IN_MAX_SLOTS ||
       (plan.in_mask & (plan.in_mask + 1)))
     return -1;
   hipStream_t s = (hipStream_t)stream;
-  const uint32_t rows_per_vec = 16u / p.nar_w;
+  const bool split = p.nar_w == 4;
+  /* a split plane streams its 2-byte high halves */
+  const uint32_t rows_per_vec = split ? 8u : 16u / p.nar_w;
   const uint64_t n_vec = (n_rows + rows_per_vec - 1) / rows_per_vec;
-  /* k_plane_fcn's grid: 2048 blocks = 8 per CU */
+  /* dev_plane_fcn_launch's grids: 2048 blocks = 8 per CU, and over a split
+     plane 768 = 3 per CU while phase one is the work, as in k_plane_fcs. Once
+     a wave's iteration (64 lanes x 32 rows) expects an open row, the probes'
+     latency is the work and more waves hide it: 2048 again. Measured at three
+     lists: tuned figures, not rules; COPR_IN_GRID overrides
+     them. A finalizing launch needs a block even over no rows, and a launch
+     that does not stream needs no more than one */
   uint64_t nb = (n_vec + 256u * COPR_PLANE_INB_UNR - 1) /
                 (256u * COPR_PLANE_INB_UNR);
-  const uint64_t cap = grid_cap ? grid_cap : 2048u;
+  const bool light = split && (uint64_t)sa.flagged * 2048u < sa.buckets;
+  const uint64_t cap = grid_cap ? grid_cap : light ? 768u : 2048u;
   if (nb > cap) nb = cap;
+  if (!nb || (split && (sa.none || fa.never))) nb = 1;
   const uint4 *data = (const uint4 *)p.nar;
+  const uint32_t mask = n_slots - 1;
+  const uint32_t in_slots = plan.in_mask + 1;
+  const unsigned long long base = (unsigned long long)p.nar_base;
+  const unsigned long long nmax = (unsigned long long)p.nar_nmax;
   if (p.nar_w == 1)
     hipLaunchKernelGGL(k_plane_inb<uint8_t>, dim3((uint32_t)nb), dim3(256), 0,
-                       s, data, n_rows, plan.in_tab, plan.in_mask + 1,
-                       plan.in_empty, (unsigned long long)p.nar_base,
-                       (unsigned long long)p.nar_nmax, fa.invert, fa.never,
-                       d_cnt);
-  else
+                       s, data, n_rows, plan.in_tab, in_slots, plan.in_empty,
+                       base, nmax, fa.invert, fa.never, d_cnt, mask, d_ticket,
+                       h_out, d_stamp, seq);
+  else if (p.nar_w == 2)
     hipLaunchKernelGGL(k_plane_inb<uint16_t>, dim3((uint32_t)nb), dim3(256), 0,
-                       s, data, n_rows, plan.in_tab, plan.in_mask + 1,
-                       plan.in_empty, (unsigned long long)p.nar_base,
-                       (unsigned long long)p.nar_nmax, fa.invert, fa.never,
-                       d_cnt);
+                       s, data, n_rows, plan.in_tab, in_slots, plan.in_empty,
+                       base, nmax, fa.invert, fa.never, d_cnt, mask, d_ticket,
+                       h_out, d_stamp, seq);
+  else
+    hipLaunchKernelGGL(k_plane_ins, dim3((uint32_t)nb), dim3(256),
+                       (size_t)in_slots * 8, s, data,
+                       (const uint4 *)((const uint8_t *)p.nar + p.nar_lo_off),
+                       n_rows, plan.in_tab, in_slots, plan.in_empty, base,
+                       nmax, sa, fa.invert, fa.never, d_cnt, mask, d_ticket,
+                       h_out, d_stamp, seq);
   return (int)hipGetLastError();
 }
 

@@ -595,7 +595,9 @@ class Engine:
         """(polled, fallbacks): one-dispatch filter+count requests whose end
         the host learnt from the polled sequence word, and those that waited
         for the stream instead (COPR_FC_POLL_US=0 or a passed deadline),
-        since the engine was created. Other branches move neither."""
+        since the engine was created. A range filter and an IN list alike:
+        count(*) alone with every region on a narrow plane. Other branches
+        move neither."""
         return (self._lib.copr_engine_fc_polled(self._h),
                 self._lib.copr_engine_fc_fallbacks(self._h))
 
@@ -607,6 +609,12 @@ class Engine:
         w, b = C.c_uint64(), C.c_uint64()
         self._lib.copr_engine_in_launches(self._h, C.byref(w), C.byref(b))
         return w.value, b.value
+
+    def in_split_launches(self):
+        """Per-region launches of k_plane_ins, the IN-list filter+count
+        kernel over a split plane (plane_stats()[0] counts them too,
+        in_stats() does not), since the engine was created."""
+        return self._lib.copr_engine_in_split_launches(self._h)
 
     def topn_stats(self):
         """(runs, kept, candidates): TopN requests served by the multi-key
