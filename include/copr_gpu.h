@@ -111,6 +111,11 @@ uint64_t    copr_engine_narrow_launches(const copr_engine *);
 uint64_t    copr_engine_narrow_builds(const copr_engine *);
 /* of the narrow launches, those over a split plane */
 uint64_t    copr_engine_split_launches(const copr_engine *);
+/* The bucket index of a split plane: narrow launches that
+ * answered from it (copr_engine_narrow_launches counts them too,
+ * copr_engine_split_launches does not), and indexes built. Monotonic. */
+uint64_t    copr_engine_bucket_launches(const copr_engine *);
+uint64_t    copr_engine_bucket_builds(const copr_engine *);
 /* The one-dispatch filter+count step: requests whose end the
  * host learnt from the sequence word it polled, and requests that waited for
  * the stream instead (deadline passed, or COPR_FC_POLL_US=0). Monotonic;

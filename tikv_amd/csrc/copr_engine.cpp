@@ -112,6 +112,14 @@ extern "C" uint64_t copr_engine_split_launches(const copr_engine *eng) {
   return eng ? eng->split_launches : 0;
 }
 
+extern "C" uint64_t copr_engine_bucket_launches(const copr_engine *eng) {
+  return eng ? eng->bucket_launches : 0;
+}
+
+extern "C" uint64_t copr_engine_bucket_builds(const copr_engine *eng) {
+  return eng ? eng->bucket_builds : 0;
+}
+
 extern "C" void copr_engine_in_launches(const copr_engine *eng, uint64_t *wide,
                                         uint64_t *bitmap) {
   if (wide) *wide = eng ? eng->in_wide_launches : 0;
@@ -1158,7 +1166,21 @@ struct NarrowUse {
   const DevRegion::ColPlane *p = nullptr;
   NarrowFcArgs nf{};
   SplitFcArgs sf{};                /* a split plane's form of nf */
+  bool bucket = false;             /* the request takes the plane's bucket
+                                      index and ba */
+  BucketFcArgs ba{};
 };
+
+/* the bucket index's row threshold, read per call:
+   COPR_NO_BUCKETS=1 neither builds nor uses an index,
+   COPR_BUCKET_MIN_ROWS=n moves the threshold */
+#define COPR_BUCKET_MIN_ROWS_DEFAULT (1ull << 22)
+static uint64_t bucket_min_rows() {
+  if (getenv("COPR_NO_BUCKETS")) return UINT64_MAX;
+  if (const char *e = getenv("COPR_BUCKET_MIN_ROWS"))
+    return (uint64_t)strtoull(e, nullptr, 10);
+  return COPR_BUCKET_MIN_ROWS_DEFAULT;
+}
 
 static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
                        PlaneSet *ps, bool hash = false,
@@ -1214,8 +1236,10 @@ static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
   PlaneFcArgs fa;
   if (nu && !hash && !getenv("COPR_NO_NARROW") &&
       dev_plane_fc_shape(sp, *ps, &fa)) {
+    const uint64_t bkt_min = bucket_min_rows();
     const DevRegion::ColPlane *np = dev_colplane_narrow(
-        dev, sp.filter_col_id, budget, eng->stream, &eng->narrow_builds);
+        dev, sp.filter_col_id, budget, eng->stream, &eng->narrow_builds,
+        bkt_min, &eng->bucket_builds);
     NarrowFcArgs nf;
     if (np && narrow_fc_fold(fa, np->nar_base, np->nar_nmax,
                              sp.filter_col_unsigned != 0, &nf)) {
@@ -1223,8 +1247,12 @@ static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
       nu->nf = nf;
       /* COPR_SPLIT_ALL_LO=1 (read per call): every row is resolved from both
          halves, the split kernel's worst case; same result bytes */
-      if (np->nar_lo_off)
-        split_fc_fold(nf, getenv("COPR_SPLIT_ALL_LO") != nullptr, &nu->sf);
+      const bool all_lo = getenv("COPR_SPLIT_ALL_LO") != nullptr;
+      if (np->nar_lo_off) split_fc_fold(nf, all_lo, &nu->sf);
+      /* an indexed plane answers from its buckets; "every row through both
+         halves of the scan" and a plane under the threshold keep the scan */
+      if (np->bkt_lo && !all_lo && dev.n_kv >= bkt_min)
+        nu->bucket = bucket_fc_fold(nu->sf, np->bkt_off, dev.n_kv, &nu->ba);
     }
   }
   return true;
@@ -2810,9 +2838,10 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
           uint64_t budget = dev.val_bytes / 2;       /* as plane_wire's */
           if (const char *e = getenv("COPR_PLANE_BUDGET_MB"))
             budget = (uint64_t)strtoull(e, nullptr, 10) << 20;
+          /* an IN list has no use for the bucket index */
           const DevRegion::ColPlane *np = dev_colplane_narrow(
               dev, pl.sp.filter_col_id, budget, eng->stream,
-              &eng->narrow_builds);
+              &eng->narrow_builds, UINT64_MAX, nullptr);
           if (!np) continue;
           if (np->nar_w <= 2) {
             in_nar[rg] = np;
@@ -2917,6 +2946,7 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             stream_bytes += regions[rg]->dev.n_kv * in_nar[rg]->nar_w;
           } else {
             e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf, nuse[rg].sf,
+                                     nuse[rg].bucket ? &nuse[rg].ba : nullptr,
                                      regions[rg]->dev.n_kv, d_cnt,
                                      COPR_FCN_SLOTS,
                                      last ? d_ticket : nullptr,
@@ -2925,7 +2955,8 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
                                      fcn_grid, eng->stream);
             eng->plane_launches++;
             eng->narrow_launches++;
-            if (nuse[rg].p->nar_lo_off) eng->split_launches++;
+            if (nuse[rg].bucket) eng->bucket_launches++;
+            else if (nuse[rg].p->nar_lo_off) eng->split_launches++;
             stream_bytes += regions[rg]->dev.n_kv * nuse[rg].p->nar_w;
           }
           if (e) {
@@ -2984,12 +3015,14 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             /* a narrow region beside regions that are not: same kernel, the
                count joins the other regions' in the usual accumulator */
             e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf, nuse[rg].sf,
+                                     nuse[rg].bucket ? &nuse[rg].ba : nullptr,
                                      regions[rg]->dev.n_kv, &d_acc[0].cnt, 1,
                                      nullptr, nullptr, nullptr, 0, fcn_grid,
                                      eng->stream);
             eng->plane_launches++;
             eng->narrow_launches++;
-            if (nuse[rg].p->nar_lo_off) eng->split_launches++;
+            if (nuse[rg].bucket) eng->bucket_launches++;
+            else if (nuse[rg].p->nar_lo_off) eng->split_launches++;
           } else if (in_planes && plane_set_used(psets[rg])) {
             if (in_nar[rg]) {
               /* one slot, no ticket: the count joins the other regions' */

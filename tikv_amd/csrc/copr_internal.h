@@ -68,6 +68,15 @@ struct DevRegion {
     int32_t nar_verdict = 0;       /* NAR_UNTRIED / NAR_DECLINED / NAR_BUILT */
     int64_t nar_base = 0;          /* signed minimum of the plane's values */
     uint64_t nar_nmax = 0;         /* max - min */
+    /* bucket index of a split plane: the low halves grouped by
+       h = n >> 16, and on the host the 65 537 offsets of the groups, bucket h
+       at [bkt_off[h], bkt_off[h + 1]). Tried once, with or after the narrow
+       build, on a plane of at least the caller's row threshold; a declined
+       verdict (over budget, an allocation or the sort failed) is remembered
+       and the plane keeps k_plane_fcs. n_kv x 2 + 65537 x 8 is charged. */
+    uint16_t *bkt_lo = nullptr;    /* [n_kv] (+ tail slack), device */
+    uint64_t *bkt_off = nullptr;   /* [COPR_N_BUCKETS + 1], host (malloc) */
+    int32_t bkt_verdict = 0;       /* NAR_UNTRIED / NAR_DECLINED / NAR_BUILT */
   };
   ColPlane planes[COPR_MAX_PLANES];
   int32_t n_planes = 0;
@@ -374,10 +383,15 @@ const DevRegion::ColPlane *dev_colplane_get(DevRegion &rgn, int64_t col_id,
 void dev_colplane_free(DevRegion &rgn);
 /* narrow companion of col_id's plane (which must exist): built on first use
  * within budget_bytes (synchronous, like dev_colplane_get), null when the
- * plane was declined. *built is incremented when this call stored one. */
+ * plane was declined. *built is incremented when this call stored one.
+ * A split plane of at least bucket_min_rows rows whose bucket index (DESIGN
+ * §9q) is untried gets it here, by this call or a later one, *bkt_built
+ * counting; UINT64_MAX = leave the index as it is. No index is no error. */
 const DevRegion::ColPlane *dev_colplane_narrow(DevRegion &rgn, int64_t col_id,
                                                uint64_t budget_bytes,
-                                               hipStream_t s, uint64_t *built);
+                                               hipStream_t s, uint64_t *built,
+                                               uint64_t bucket_min_rows,
+                                               uint64_t *bkt_built);
 /* does the request take k_plane_fc on this wiring? On true *fa is its range
  * test. */
 bool dev_plane_fc_shape(const ScanPlan &plan, const PlaneSet &ps,
@@ -393,14 +407,16 @@ bool dev_plane_fc_shape(const ScanPlan &plan, const PlaneSet &ps,
  * leaves the wall clock it read at entry in that word, which is the u64
  * COPR_FCN_STAMP_WORD behind the ticket. grid_cap 0 = the default grid. A
  * split plane (width 4) takes k_plane_fcs and sf, the others k_plane_fcn<T>
- * and nf. */
+ * and nf. A non-null ba (bucket_fc_fold over the plane's bucket index, DESIGN
+ * §9q) sends a split plane to k_plane_fcb: one launch over the edge buckets'
+ * low halves, same count words and same finalizing tail. */
 #define COPR_FCN_SLOTS 64
 #define COPR_FCN_SLOT_STRIDE 16          /* u64 words: one 128 B line each */
 #define COPR_FCN_STATE_WORDS (COPR_FCN_SLOTS * COPR_FCN_SLOT_STRIDE + 16)
 #define COPR_FCN_STAMP_WORD 1            /* u64 words behind the ticket */
 int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
-                         const SplitFcArgs &sf, uint64_t n_rows,
-                         unsigned long long *d_cnt,
+                         const SplitFcArgs &sf, const BucketFcArgs *ba,
+                         uint64_t n_rows, unsigned long long *d_cnt,
                          uint32_t n_slots, unsigned int *d_ticket,
                          unsigned long long *h_out,
                          unsigned long long *d_stamp, unsigned long long seq,
@@ -674,6 +690,10 @@ struct copr_engine {
   uint64_t narrow_launches = 0;
   uint64_t narrow_builds = 0;
   uint64_t split_launches = 0;     /* narrow launches that took k_plane_fcs */
+  /* copr_engine_bucket_launches / _builds: narrow launches that
+     took k_plane_fcb, and bucket indexes built */
+  uint64_t bucket_launches = 0;
+  uint64_t bucket_builds = 0;
   /* one-dispatch requests that ended on the polled word / on the stream wait
      (copr_engine_fc_polled / _fc_fallbacks) */
   uint64_t fc_polled = 0;

@@ -2101,6 +2101,8 @@ void dev_colplane_free(DevRegion &rgn) {
     hipFree(rgn.planes[i].val);
     hipFree(rgn.planes[i].st);
     hipFree(rgn.planes[i].nar);
+    hipFree(rgn.planes[i].bkt_lo);
+    free(rgn.planes[i].bkt_off);
     rgn.planes[i] = DevRegion::ColPlane{};
   }
   rgn.n_planes = 0;

@@ -2,6 +2,7 @@
  * filter+count kernel over them. The wide planes, their build
  * and their consumers live in kernels.hip. */
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
 #include "copr_internal.h"
 #include "fc_wait.h"                     /* FCW_* host word indices */
 
@@ -96,9 +97,99 @@ k_plane_split(const longlong2 *__restrict__ val, uint64_t n_rows, int64_t base,
   }
 }
 
+/* ---------------- a split plane's bucket index ----------------
+ * off[h] = the first position of the sorted high halves holding a key >= h,
+ * h = 0 .. 65536: one lane per h, a binary search each. */
+__global__ void __launch_bounds__(256)
+k_bucket_offsets(const uint16_t *__restrict__ keys, uint64_t n_rows,
+                 unsigned long long *__restrict__ off) {
+  const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
+  if (h > COPR_N_BUCKETS) return;
+  uint64_t lo = 0, hi = n_rows;
+  while (lo < hi) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if ((uint32_t)keys[mid] < h) lo = mid + 1;
+    else hi = mid;
+  }
+  off[h] = lo;
+}
+
+/* One stable radix sort of (H, L) pairs by H, the offsets from the sorted
+   keys, one copy of them to the host. The sorted keys and the sort's
+   temporary storage live for this call only. Whatever fails, the plane is as
+   it was but for the verdict. */
+static void bucket_index_build(DevRegion &rgn, DevRegion::ColPlane *p,
+                               uint64_t budget_bytes, hipStream_t s,
+                               uint64_t *built) {
+  p->bkt_verdict = NAR_DECLINED;
+  const uint64_t n = rgn.n_kv;
+  const uint64_t off_bytes = (uint64_t)(COPR_N_BUCKETS + 1) * 8;
+  const uint64_t cost = n * 2 + off_bytes;
+  /* the sort has not been run here beyond 32-bit sizes */
+  if (rgn.plane_bytes + cost > budget_bytes || n > 0xFFFFFFFFull) return;
+  const uint16_t *hi = (const uint16_t *)p->nar;
+  const uint16_t *lo = (const uint16_t *)((const uint8_t *)p->nar + p->nar_lo_off);
+  uint16_t *d_keys = nullptr, *d_lo = nullptr;
+  unsigned long long *d_off = nullptr;
+  void *d_tmp = nullptr;
+  uint64_t *h_off = (uint64_t *)malloc(off_bytes);
+  size_t tmp_bytes = 0;
+  bool ok = h_off != nullptr;
+  ok = ok && rocprim::radix_sort_pairs(nullptr, tmp_bytes, hi, d_keys, lo, d_lo,
+                                       (size_t)n, 0, 16, s) == hipSuccess;
+  ok = ok && hipMalloc((void **)&d_keys, n * 2) == hipSuccess;
+  ok = ok && hipMalloc((void **)&d_lo, n * 2 + 2048) == hipSuccess;
+  ok = ok && hipMalloc((void **)&d_off, off_bytes) == hipSuccess;
+  ok = ok && hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 1) == hipSuccess;
+  ok = ok && rocprim::radix_sort_pairs(d_tmp, tmp_bytes, hi, d_keys, lo, d_lo,
+                                       (size_t)n, 0, 16, s) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_bucket_offsets, dim3((COPR_N_BUCKETS + 1 + 255) / 256),
+                       dim3(256), 0, s, d_keys, n, d_off);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  ok = ok && hipMemcpyAsync(h_off, d_off, off_bytes, hipMemcpyDeviceToHost,
+                            s) == hipSuccess;
+  ok = ok && hipStreamSynchronize(s) == hipSuccess;
+  /* what bucket_fc_fold relies on, checked once here */
+  ok = ok && h_off[0] == 0 && h_off[COPR_N_BUCKETS] == n;
+  for (uint32_t h = 0; ok && h < COPR_N_BUCKETS; h++)
+    ok = h_off[h] <= h_off[h + 1];
+  if (!ok) (void)hipGetLastError();
+  hipFree(d_tmp);
+  hipFree(d_keys);
+  hipFree(d_off);
+  if (!ok) {
+    hipFree(d_lo);
+    free(h_off);
+    return;
+  }
+  p->bkt_lo = d_lo;
+  p->bkt_off = h_off;
+  p->bkt_verdict = NAR_BUILT;
+  rgn.plane_bytes += cost;
+  if (built) (*built)++;
+}
+
+static DevRegion::ColPlane *narrow_plane(DevRegion &rgn, int64_t col_id,
+                                         uint64_t budget_bytes, hipStream_t s,
+                                         uint64_t *built);
+
 const DevRegion::ColPlane *dev_colplane_narrow(DevRegion &rgn, int64_t col_id,
                                                uint64_t budget_bytes,
-                                               hipStream_t s, uint64_t *built) {
+                                               hipStream_t s, uint64_t *built,
+                                               uint64_t bucket_min_rows,
+                                               uint64_t *bkt_built) {
+  DevRegion::ColPlane *p = narrow_plane(rgn, col_id, budget_bytes, s, built);
+  if (p && p->nar_lo_off && p->bkt_verdict == NAR_UNTRIED &&
+      rgn.n_kv >= bucket_min_rows)
+    bucket_index_build(rgn, p, budget_bytes, s, bkt_built);
+  return p;
+}
+
+static DevRegion::ColPlane *narrow_plane(DevRegion &rgn, int64_t col_id,
+                                         uint64_t budget_bytes, hipStream_t s,
+                                         uint64_t *built) {
   DevRegion::ColPlane *p = nullptr;
   for (int32_t i = 0; i < rgn.n_planes; i++)
     if (rgn.planes[i].col_id == col_id && rgn.planes[i].val)
@@ -530,6 +621,102 @@ k_plane_fcs(const uint4 *__restrict__ hi, const uint4 *__restrict__ lo,
   fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out, stamp, t_entry, seq);
 }
 
+/* Filter+count over a split plane's bucket index. The host has
+ * counted the rows whose bucket decides them from two offsets (add, which
+ * block 0 brings to the tail), so the kernel reads only the edge buckets' low
+ * halves: up to two slices [beg, end) of bkt_lo, each with its h.
+ * k_plane_fcn<uint16_t>'s shape over the concatenation of the two slices'
+ * 16 B vectors: slice i covers the vectors vb[i] = beg / 8 up to
+ * ceil(end / 8), vn[i] of them, a slice's first and last vector shared with
+ * its neighbours in bkt_lo and masked by [beg, end). Loads are clamped to the
+ * last vector of the concatenation, which may reach 14 B into the tail slack.
+ * Within one bucket the full test is a 16-bit range test on l, so an iteration
+ * whose every row is inside one slice is counted packed; the
+ * others put each live row through split_full_in. A kept row is in != invert,
+ * so add is the rows decided without a look that the request keeps. */
+__global__ void __launch_bounds__(256)
+k_plane_fcb(const uint4 *__restrict__ data, BucketFcArgs ba, SplitFcArgs sf,
+            unsigned long long add,
+            unsigned long long *__restrict__ cnt_out, uint32_t slot_mask,
+            unsigned int *__restrict__ ticket,
+            unsigned long long *__restrict__ h_out,
+            unsigned long long *__restrict__ stamp, unsigned long long seq) {
+  const unsigned long long t_entry = fcn_entry_clock(stamp);
+  constexpr int UNR = 4;
+  constexpr uint32_t R = 8;                        /* rows per 16 B */
+  const bool inv = ba.invert != 0;
+  unsigned long long cnt =
+      (blockIdx.x == 0 && threadIdx.x == 0) ? add : 0ull;
+  uint64_t vb[2] = {0, 0}, vn[2] = {0, 0};
+  uint32_t l_lo_pk[2] = {0, 0}, l_span_pk[2] = {0, 0};
+  #pragma unroll
+  for (uint32_t i = 0; i < 2; i++)
+    if (i < ba.n_slices && ba.end[i] > ba.beg[i]) {
+      vb[i] = ba.beg[i] / R;
+      vn[i] = (ba.end[i] + R - 1) / R - vb[i];
+      /* [lo, lo + span] cut down to bucket h: not empty, h is a maybe bucket */
+      const uint32_t b0 = ba.h[i] << 16, hi_end = sf.lo + sf.span;
+      const uint32_t a = sf.lo > b0 ? sf.lo : b0;
+      const uint32_t b = hi_end < (b0 | 0xFFFFu) ? hi_end : (b0 | 0xFFFFu);
+      l_lo_pk[i] = fold_pack16(a & 0xFFFFu);
+      l_span_pk[i] = fold_pack16(b - a);
+    }
+  const uint64_t n_vec = vn[0] + vn[1];
+  const uint64_t step = (uint64_t)gridDim.x * 256u * UNR;
+  /* b0 = p0 - threadIdx.x, the block's first vector (uniform) */
+  uint64_t b0 = (uint64_t)blockIdx.x * 256u * UNR;
+  for (uint64_t p0 = b0 + threadIdx.x; p0 < n_vec; p0 += step, b0 += step) {
+    uint4 v[UNR];
+    /* the slice of the block's first and last vector (uniform) */
+    const uint32_t s0 = b0 >= vn[0] ? 1u : 0u;
+    const uint64_t e0 = b0 + 256u * UNR - 1;
+    const uint32_t s1 = e0 >= vn[0] ? 1u : 0u;
+    const uint64_t q0 = vb[s0] + (b0 - (s0 ? vn[0] : 0));   /* in bkt_lo */
+    if (e0 < n_vec && s0 == s1 && q0 * R >= ba.beg[s0] &&
+        (q0 + 256u * UNR) * R <= ba.end[s0]) {
+      const uint4 *src = data + q0 + threadIdx.x;
+      #pragma unroll
+      for (int u = 0; u < UNR; u++) v[u] = src[(uint64_t)u * 256u];
+      __builtin_amdgcn_sched_barrier(0);
+      uint32_t acc = 0;
+      #pragma unroll
+      for (int u = 0; u < UNR; u++)
+        acc = packed_out_acc(v[u], l_lo_pk[s0], l_span_pk[s0], acc);
+      const uint32_t out = packed_sum(acc);
+      cnt += inv ? out : UNR * R - out;
+      continue;
+    }
+    uint64_t q[UNR];
+    uint32_t sl[UNR];
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      const uint64_t p = min(p0 + (uint64_t)u * 256u, n_vec - 1);
+      sl[u] = p >= vn[0] ? 1u : 0u;
+      q[u] = vb[sl[u]] + (p - (sl[u] ? vn[0] : 0));
+      v[u] = data[q[u]];
+    }
+    /* all four loads issue before the first is used */
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t c = 0;
+    #pragma unroll
+    for (int u = 0; u < UNR; u++) {
+      if (p0 + (uint64_t)u * 256u >= n_vec) continue;
+      const uint64_t beg = ba.beg[sl[u]], end = ba.end[sl[u]];
+      const uint32_t h = ba.h[sl[u]];
+      const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+      #pragma unroll
+      for (uint32_t j = 0; j < R; j++) {
+        const uint64_t row = q[u] * R + j;
+        const uint32_t l = (j & 1u) ? w[j / 2] >> 16 : w[j / 2] & 0xFFFFu;
+        const bool keep = split_full_in(h, l, sf) != inv;
+        c += (row >= beg && row < end && keep) ? 1u : 0u;
+      }
+    }
+    cnt += c;
+  }
+  fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out, stamp, t_entry, seq);
+}
+
 /* IN-list filter+count over a narrow plane of 1 or 2 bytes per row (DESIGN
  * §9o). A stored n = v - base lies in [0, nmax], nmax < 2^(8 sizeof(T)), so
  * the list turns into a bitmap over that domain: 32 B for one byte, 8 KiB for
@@ -829,8 +1016,8 @@ int dev_plane_inn_launch(const DevRegion::ColPlane &p, const ScanPlan &plan,
 }
 
 int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
-                         const SplitFcArgs &sf, uint64_t n_rows,
-                         unsigned long long *d_cnt,
+                         const SplitFcArgs &sf, const BucketFcArgs *ba,
+                         uint64_t n_rows, unsigned long long *d_cnt,
                          uint32_t n_slots, unsigned int *d_ticket,
                          unsigned long long *h_out,
                          unsigned long long *d_stamp, unsigned long long seq,
@@ -859,6 +1046,32 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
   if (!nb) nb = 1;
   const uint4 *data = (const uint4 *)p.nar;
   const uint32_t mask = n_slots - 1;
+  if (ba) {
+    /* the bucket index: one block per 8192 slice rows, at least
+       one, under the split plane's cap. The slices are checked against the
+       plane once more here: the kernel trusts them */
+    if (!p.bkt_lo || !p.nar_lo_off || ba->n_slices > 2 || ba->sure > n_rows)
+      return -1;
+    uint64_t slice_rows = 0, vecs = 0;
+    for (uint32_t i = 0; i < ba->n_slices; i++) {
+      if (ba->beg[i] > ba->end[i] || ba->end[i] > n_rows ||
+          ba->h[i] >= COPR_N_BUCKETS)
+        return -1;
+      slice_rows += ba->end[i] - ba->beg[i];
+      if (ba->end[i] > ba->beg[i])
+        vecs += (ba->end[i] + 7) / 8 - ba->beg[i] / 8;
+    }
+    if (ba->sure + slice_rows > n_rows) return -1;
+    uint64_t bb = (vecs + 256u * 4 - 1) / (256u * 4);
+    if (bb > cap) bb = cap;
+    if (!bb) bb = 1;
+    const unsigned long long add =
+        ba->invert ? n_rows - ba->sure - slice_rows : ba->sure;
+    hipLaunchKernelGGL(k_plane_fcb, dim3((uint32_t)bb), dim3(256), 0, s,
+                       (const uint4 *)p.bkt_lo, *ba, sf, add, d_cnt, mask,
+                       d_ticket, h_out, d_stamp, seq);
+    return (int)hipGetLastError();
+  }
   switch (p.nar_w) {
     case 1:
       hipLaunchKernelGGL(k_plane_fcn<uint8_t>, dim3((uint32_t)nb), dim3(256),

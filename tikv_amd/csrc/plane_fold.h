@@ -201,5 +201,50 @@ COPR_FOLD_HD inline bool split_row_in(uint32_t h, uint32_t l,
   return split_full_in(h, l, sf);
 }
 
+/* k_plane_fcb: a split plane's bucket index holds the low halves
+   grouped by h and off[0 .. 65536], bucket h at [off[h], off[h + 1]). The rows
+   of the sure interval are counted by two offsets; a maybe bucket that is not
+   sure, the one holding a >> 16 and the one holding b >> 16, is a slice
+   [beg, end) of the grouped low halves whose rows take split_full_in(h, l).
+   n_slices = 1 when a >> 16 == b >> 16, 0 when both edge buckets are sure; a
+   slice may be empty. in = sure + the slices' rows that pass, and
+   count = invert ? n_rows - in : in. */
+#define COPR_N_BUCKETS 65536u
+struct BucketFcArgs {
+  uint64_t sure;                   /* rows in the sure interval */
+  uint64_t beg[2], end[2];         /* beg <= end <= n_rows */
+  uint32_t h[2];
+  uint32_t n_slices;
+  uint32_t invert;
+};
+
+/* SplitFcArgs (not the all_lo form) + offsets -> BucketFcArgs. off must be
+   non-decreasing with off[65536] == n_rows; false = it is not, at the entries
+   this request reads, and the request keeps the scan. */
+inline bool bucket_fc_fold(const SplitFcArgs &sf, const uint64_t *off,
+                           uint64_t n_rows, BucketFcArgs *ba) {
+  *ba = BucketFcArgs{};
+  ba->invert = sf.invert;
+  if (!sf.sure_empty) {
+    const uint64_t s0 = off[sf.sure_lo], s1 = off[sf.sure_lo + sf.sure_span + 1];
+    if (s0 > s1 || s1 > n_rows) return false;
+    ba->sure = s1 - s0;
+  }
+  const uint32_t ha = sf.maybe_lo, hb = sf.maybe_lo + sf.maybe_span;
+  const uint32_t edge[2] = {ha, hb};
+  for (int i = 0; i < (ha == hb ? 1 : 2); i++) {
+    const uint32_t h = edge[i];
+    if (h >= COPR_N_BUCKETS) return false;
+    if (split_sure(h, sf)) continue;
+    const uint64_t b = off[h], e = off[h + 1];
+    if (b > e || e > n_rows) return false;
+    ba->h[ba->n_slices] = h;
+    ba->beg[ba->n_slices] = b;
+    ba->end[ba->n_slices] = e;
+    ba->n_slices++;
+  }
+  return true;
+}
+
 }  // namespace copr
 #endif

@@ -591,6 +591,14 @@ class Engine:
         a split plane, i.e. took k_plane_fcs, since the engine was created."""
         return self._lib.copr_engine_split_launches(self._h)
 
+    def bucket_stats(self):
+        """(launches, builds): narrow launches that answered from a split
+        plane's bucket index, i.e. took k_plane_fcb (narrow_stats()[0] counts
+        them too, split_launches() does not), and bucket indexes built, since
+        the engine was created."""
+        return (self._lib.copr_engine_bucket_launches(self._h),
+                self._lib.copr_engine_bucket_builds(self._h))
+
     def fc_wait_stats(self):
         """(polled, fallbacks): one-dispatch filter+count requests whose end
         the host learnt from the polled sequence word, and those that waited

@@ -2,7 +2,8 @@
 the benchmark's cfg2 request over one resident region, 5 warm-up calls and 20
 timed ones, and prints for each timed call the kernel's time_processed_ns and
 the host-clock time of the call. Run it under a kernel tracer and the last 20
-k_plane_fcs dispatches of the trace are these 20 calls: tracer's duration
+k_plane_fcs dispatches (k_plane_fcb on a plane with a bucket index,
+DESIGN.md §9q) of the trace are these 20 calls: tracer's duration
 minus time_processed_ns is the dispatch ramp the in-kernel figure leaves out,
 and the check on "block 0 first". Dev tool (GPU box), not part of the product
 or bench contract.
