@@ -116,6 +116,11 @@ uint64_t    copr_engine_split_launches(const copr_engine *);
  * copr_engine_split_launches does not), and indexes built. Monotonic. */
 uint64_t    copr_engine_bucket_launches(const copr_engine *);
 uint64_t    copr_engine_bucket_builds(const copr_engine *);
+/* Two conditions over two columns: narrow launches that read
+ * both columns' narrow planes in one kernel (copr_engine_narrow_launches
+ * counts them too, copr_engine_split_launches and _bucket_launches do not).
+ * Monotonic. */
+uint64_t    copr_engine_pair_launches(const copr_engine *);
 /* The one-dispatch filter+count step: requests whose end the
  * host learnt from the sequence word it polled, and requests that waited for
  * the stream instead (deadline passed, or COPR_FC_POLL_US=0). Monotonic;

@@ -175,6 +175,8 @@ def load_lib():
     lib.copr_engine_bucket_launches.argtypes = [C.c_void_p]
     lib.copr_engine_bucket_builds.restype = C.c_uint64
     lib.copr_engine_bucket_builds.argtypes = [C.c_void_p]
+    lib.copr_engine_pair_launches.restype = C.c_uint64
+    lib.copr_engine_pair_launches.argtypes = [C.c_void_p]
     lib.copr_engine_fc_polled.restype = C.c_uint64
     lib.copr_engine_fc_polled.argtypes = [C.c_void_p]
     lib.copr_engine_fc_fallbacks.restype = C.c_uint64

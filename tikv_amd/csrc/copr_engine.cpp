@@ -115,6 +115,9 @@ extern "C" uint64_t copr_engine_split_launches(const copr_engine *eng) {
 extern "C" uint64_t copr_engine_bucket_launches(const copr_engine *eng) {
   return eng ? eng->bucket_launches : 0;
 }
+extern "C" uint64_t copr_engine_pair_launches(const copr_engine *eng) {
+  return eng ? eng->pair_launches : 0;
+}
 
 extern "C" uint64_t copr_engine_bucket_builds(const copr_engine *eng) {
   return eng ? eng->bucket_builds : 0;
@@ -1169,6 +1172,10 @@ struct NarrowUse {
   bool bucket = false;             /* the request takes the plane's bucket
                                       index and ba */
   BucketFcArgs ba{};
+  /* two conditions over two columns: p and sf are side A, p2 and
+     sf2 side B, p no wider than p2; k_plane_fc2 */
+  const DevRegion::ColPlane *p2 = nullptr;
+  SplitFcArgs sf2{};
 };
 
 /* the bucket index's row threshold, read per call:
@@ -1253,6 +1260,44 @@ static bool plane_wire(copr_engine *eng, DevRegion &dev, const ScanPlan &sp,
          halves of the scan" and a plane under the threshold keep the scan */
       if (np->bkt_lo && !all_lo && dev.n_kv >= bkt_min)
         nu->bucket = bucket_fc_fold(nu->sf, np->bkt_off, dev.n_kv, &nu->ba);
+    }
+    return true;
+  }
+  /* cmp(a, ca) AND cmp(b, cb) over two columns takes both narrow
+     companions, without a bucket index, whose rows are regrouped per column.
+     COPR_NO_PAIR=1 (read per call) leaves the request on k_plane_agg; same
+     result bytes */
+  PlaneFcArgs fb;
+  if (nu && !hash && !getenv("COPR_NO_NARROW") && !getenv("COPR_NO_PAIR") &&
+      dev_plane_fc2_shape(sp, *ps, &fa, &fb)) {
+    const DevRegion::ColPlane *pa = dev_colplane_narrow(
+        dev, sp.filter_col_id, budget, eng->stream, &eng->narrow_builds,
+        UINT64_MAX, nullptr);
+    const DevRegion::ColPlane *pb =
+        pa ? dev_colplane_narrow(dev, sp.filter2_col_id, budget, eng->stream,
+                                 &eng->narrow_builds, UINT64_MAX, nullptr)
+           : nullptr;
+    NarrowFcArgs na, nb;
+    if (pa && pb &&
+        narrow_fc_fold(fa, pa->nar_base, pa->nar_nmax,
+                       sp.filter_col_unsigned != 0, &na) &&
+        narrow_fc_fold(fb, pb->nar_base, pb->nar_nmax,
+                       sp.filter2_col_unsigned != 0, &nb)) {
+      const bool all_lo = getenv("COPR_SPLIT_ALL_LO") != nullptr;
+      auto side = [&](const DevRegion::ColPlane *p, const NarrowFcArgs &nf,
+                      SplitFcArgs *sf) {
+        *sf = SplitFcArgs{};
+        sf->lo = nf.lo;
+        sf->span = nf.span;
+        sf->invert = nf.invert;
+        if (p->nar_lo_off) split_fc_fold(nf, all_lo, sf);
+      };
+      /* AND commutes: the narrower plane is side A */
+      const bool swap = pa->nar_w > pb->nar_w;
+      nu->p = swap ? pb : pa;
+      nu->p2 = swap ? pa : pb;
+      side(nu->p, swap ? nb : na, &nu->sf);
+      side(nu->p2, swap ? na : nb, &nu->sf2);
     }
   }
   return true;
@@ -2875,6 +2920,35 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
       uint32_t fcn_grid = 0;   /* diagnostic: cap k_plane_fcn / _fcs' grid */
       if (const char *g = getenv("COPR_NARROW_GRID"))
         fcn_grid = (uint32_t)strtoul(g, nullptr, 10);
+      /* one launch of a range request over a region's narrow plane or, for two
+         conditions over two columns, planes; its counters.
+         *bytes = what the launch can read */
+      auto narrow_launch = [&](uint32_t rg, unsigned long long *d_cnt,
+                               uint32_t n_slots, unsigned int *d_ticket,
+                               unsigned long long *h_out,
+                               unsigned long long *d_stamp,
+                               unsigned long long seq, uint64_t *bytes) -> int {
+        const NarrowUse &u = nuse[rg];
+        const uint64_t n_kv = regions[rg]->dev.n_kv;
+        int e;
+        eng->plane_launches++;
+        eng->narrow_launches++;
+        if (u.p2) {
+          e = dev_plane_fc2_launch(*u.p, u.sf, *u.p2, u.sf2, n_kv, d_cnt,
+                                   n_slots, d_ticket, h_out, d_stamp, seq,
+                                   fcn_grid, eng->stream);
+          eng->pair_launches++;
+          if (bytes) *bytes += n_kv * (u.p->nar_w + u.p2->nar_w);
+          return e;
+        }
+        e = dev_plane_fcn_launch(*u.p, u.nf, u.sf, u.bucket ? &u.ba : nullptr,
+                                 n_kv, d_cnt, n_slots, d_ticket, h_out,
+                                 d_stamp, seq, fcn_grid, eng->stream);
+        if (u.bucket) eng->bucket_launches++;
+        else if (u.p->nar_lo_off) eng->split_launches++;
+        if (bytes) *bytes += n_kv * u.p->nar_w;
+        return e;
+      };
       /* one-dispatch step: every region takes k_plane_fcn (or,
          on a split plane, k_plane_fcs), so
          the whole result is one count, which the last launch's last block
@@ -2945,19 +3019,10 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
                                  rg == 0 ? d_stamp : nullptr, seq);
             stream_bytes += regions[rg]->dev.n_kv * in_nar[rg]->nar_w;
           } else {
-            e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf, nuse[rg].sf,
-                                     nuse[rg].bucket ? &nuse[rg].ba : nullptr,
-                                     regions[rg]->dev.n_kv, d_cnt,
-                                     COPR_FCN_SLOTS,
-                                     last ? d_ticket : nullptr,
-                                     last ? eng->h_fcn_out : nullptr,
-                                     rg == 0 ? d_stamp : nullptr, seq,
-                                     fcn_grid, eng->stream);
-            eng->plane_launches++;
-            eng->narrow_launches++;
-            if (nuse[rg].bucket) eng->bucket_launches++;
-            else if (nuse[rg].p->nar_lo_off) eng->split_launches++;
-            stream_bytes += regions[rg]->dev.n_kv * nuse[rg].p->nar_w;
+            e = narrow_launch(rg, d_cnt, COPR_FCN_SLOTS,
+                              last ? d_ticket : nullptr,
+                              last ? eng->h_fcn_out : nullptr,
+                              rg == 0 ? d_stamp : nullptr, seq, &stream_bytes);
           }
           if (e) {
             eng->fcn_dirty = true;
@@ -3014,15 +3079,8 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
           if (!nuse.empty() && nuse[rg].p) {
             /* a narrow region beside regions that are not: same kernel, the
                count joins the other regions' in the usual accumulator */
-            e = dev_plane_fcn_launch(*nuse[rg].p, nuse[rg].nf, nuse[rg].sf,
-                                     nuse[rg].bucket ? &nuse[rg].ba : nullptr,
-                                     regions[rg]->dev.n_kv, &d_acc[0].cnt, 1,
-                                     nullptr, nullptr, nullptr, 0, fcn_grid,
-                                     eng->stream);
-            eng->plane_launches++;
-            eng->narrow_launches++;
-            if (nuse[rg].bucket) eng->bucket_launches++;
-            else if (nuse[rg].p->nar_lo_off) eng->split_launches++;
+            e = narrow_launch(rg, &d_acc[0].cnt, 1, nullptr, nullptr, nullptr,
+                              0, nullptr);
           } else if (in_planes && plane_set_used(psets[rg])) {
             if (in_nar[rg]) {
               /* one slot, no ticket: the count joins the other regions' */

@@ -421,6 +421,24 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
                          unsigned long long *h_out,
                          unsigned long long *d_stamp, unsigned long long seq,
                          uint32_t grid_cap, void *stream);
+/* Two conditions over two columns. dev_plane_fc2_shape: does the
+ * request, count(*) under cmp(col a, const) AND cmp(col b, const) over two
+ * distinct int columns, fit k_plane_fc2 on this wiring? On true *fa and *fb
+ * are the two range tests. dev_plane_fc2_launch: one launch over the narrow
+ * companions of both columns, pa no wider than pb (AND commutes; the caller
+ * orders them). sa and sb carry each side's test: lo, span and invert of
+ * narrow_fc_fold for a 1- or 2-byte plane, all of split_fc_fold for a split
+ * one. Count words, ticket, stamp, seq and grid_cap are
+ * dev_plane_fcn_launch's. */
+bool dev_plane_fc2_shape(const ScanPlan &plan, const PlaneSet &ps,
+                         PlaneFcArgs *fa, PlaneFcArgs *fb);
+int dev_plane_fc2_launch(const DevRegion::ColPlane &pa, const SplitFcArgs &sa,
+                         const DevRegion::ColPlane &pb, const SplitFcArgs &sb,
+                         uint64_t n_rows, unsigned long long *d_cnt,
+                         uint32_t n_slots, unsigned int *d_ticket,
+                         unsigned long long *h_out,
+                         unsigned long long *d_stamp, unsigned long long seq,
+                         uint32_t grid_cap, void *stream);
 /* simple aggregates (mode 1) over column planes instead of the row bytes */
 int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
                          const DevRegion &rgn, SimpleAggAcc *d_simple,
@@ -694,6 +712,9 @@ struct copr_engine {
      took k_plane_fcb, and bucket indexes built */
   uint64_t bucket_launches = 0;
   uint64_t bucket_builds = 0;
+  /* copr_engine_pair_launches: narrow launches that took
+     k_plane_fc2 over two columns' planes */
+  uint64_t pair_launches = 0;
   /* one-dispatch requests that ended on the polled word / on the stream wait
      (copr_engine_fc_polled / _fc_fallbacks) */
   uint64_t fc_polled = 0;

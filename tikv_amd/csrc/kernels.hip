@@ -2411,20 +2411,57 @@ k_plane_fc(PlaneFcArgs fa, const longlong2 *__restrict__ val,
 static bool plane_fc_args(const ScanPlan &plan, const PlaneSet &ps,
                           PlaneFcArgs *fa) {
   if (plan.n_aggs != 1 || plan.aggs[0].kind != DAGG_COUNT_ROWS ||
-      !plan.has_filter || !ps.f.val || ps.f2.val || plan.filter2_on ||
+      !plan.has_filter || !ps.f.val ||
       plan.filter_is_real || plan.filter_decode_only ||
       (plan.filter_col_unsigned != 0) != (plan.filter_const_unsigned != 0) ||
       ps.f.n_rowparse)
     return false;
+  if (!plan.filter2_on) {
+    if (ps.f2.val) return false;
+    plane_fc_fold(plan.filter_cmp, plan.filter_const,
+                  plan.filter_col_unsigned != 0, plan.filter_const_null != 0,
+                  plan.filter_missing_null != 0, plan.filter_missing_val, fa);
+    return true;
+  }
+  /* two conditions on one column fold into one interval where they can
+     (DESIGN §9r); both channels are then wired to the same plane */
+  if (plan.filter2_col_id != plan.filter_col_id || plan.filter2_is_real ||
+      (ps.f2.val && ps.f2.val != ps.f.val) ||
+      (plan.filter2_col_unsigned != 0) != (plan.filter_col_unsigned != 0) ||
+      (plan.filter2_col_unsigned != 0) != (plan.filter2_const_unsigned != 0))
+    return false;
+  PlaneFcArgs a, b;
   plane_fc_fold(plan.filter_cmp, plan.filter_const,
                 plan.filter_col_unsigned != 0, plan.filter_const_null != 0,
-                plan.filter_missing_null != 0, plan.filter_missing_val, fa);
-  return true;
+                plan.filter_missing_null != 0, plan.filter_missing_val, &a);
+  plane_fc_fold(plan.filter2_cmp, plan.filter2_const,
+                plan.filter2_col_unsigned != 0, plan.filter2_const_null != 0,
+                plan.filter2_missing_null != 0, plan.filter2_missing_val, &b);
+  return plane_fc_and(a, b, fa);
 }
 
 bool dev_plane_fc_shape(const ScanPlan &plan, const PlaneSet &ps,
                         PlaneFcArgs *fa) {
   return plane_fc_args(plan, ps, fa);
+}
+
+bool dev_plane_fc2_shape(const ScanPlan &plan, const PlaneSet &ps,
+                         PlaneFcArgs *fa, PlaneFcArgs *fb) {
+  if (plan.n_aggs != 1 || plan.aggs[0].kind != DAGG_COUNT_ROWS ||
+      !plan.has_filter || !plan.filter2_on || !ps.f.val || !ps.f2.val ||
+      plan.filter2_col_id == plan.filter_col_id ||
+      plan.filter_is_real || plan.filter2_is_real || plan.filter_decode_only ||
+      (plan.filter_col_unsigned != 0) != (plan.filter_const_unsigned != 0) ||
+      (plan.filter2_col_unsigned != 0) != (plan.filter2_const_unsigned != 0) ||
+      ps.f.n_rowparse || ps.f2.n_rowparse)
+    return false;
+  plane_fc_fold(plan.filter_cmp, plan.filter_const,
+                plan.filter_col_unsigned != 0, plan.filter_const_null != 0,
+                plan.filter_missing_null != 0, plan.filter_missing_val, fa);
+  plane_fc_fold(plan.filter2_cmp, plan.filter2_const,
+                plan.filter2_col_unsigned != 0, plan.filter2_const_null != 0,
+                plan.filter2_missing_null != 0, plan.filter2_missing_val, fb);
+  return true;
 }
 
 int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,

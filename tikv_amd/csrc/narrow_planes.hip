@@ -717,6 +717,169 @@ k_plane_fcb(const uint4 *__restrict__ data, BucketFcArgs ba, SplitFcArgs sf,
   fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out, stamp, t_entry, seq);
 }
 
+/* ---------------- two conditions over two columns -------------
+ * count(*) WHERE cmp(a, ca) AND cmp(b, cb) over the narrow companions of both
+ * columns. W is a side's width, 1, 2 or 4 = split, and WA <= WB (the host
+ * orders the sides). A lane's unit is 16 consecutive rows, the same rows of
+ * both planes: one 16 B vector of a 1-byte plane, two of a 2-byte plane or of
+ * a split plane's halves. An iteration takes two units per lane, unit u of
+ * lane t at b0 + 256 u + t, so a row mask is one word: unit u's row j is bit
+ * 16 u + j, which is bit 8 k + j of a 2-byte side's vector k = 2 u + (j >> 3).
+ * The helpers below take a side's vectors as an array of four; a 1-byte side
+ * uses the first two. */
+
+/* the index of a side's vector k, clamped to the plane's last vector */
+template <int W>
+__device__ __forceinline__ uint64_t
+fc2_vec(const uint64_t (&q)[2], int k, uint64_t n_vec) {
+  const uint64_t p = W == 1 ? q[k] : 2 * q[k >> 1] + (uint64_t)(k & 1);
+  return min(p, n_vec - 1);
+}
+
+/* phase one of a side: in = the rows the loaded bytes put inside the
+   interval, open = the rows they cannot decide (a split side's maybe and not
+   sure). A 1- or 2-byte side decides every row by k_plane_fcn's test. */
+template <int W>
+__device__ __forceinline__ void
+fc2_classify(const uint4 (&v)[4], const SplitFcArgs &sf, uint32_t &in,
+             uint32_t &open) {
+  in = 0;
+  open = 0;
+  #pragma unroll
+  for (int k = 0; k < (W == 1 ? 2 : 4); k++) {
+    const uint32_t w[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+    if constexpr (W == 1) {
+      #pragma unroll
+      for (uint32_t j = 0; j < 16; j++) {
+        const uint32_t n = (w[j / 4] >> (8u * (j % 4))) & 0xFFu;
+        in |= ((n - sf.lo) <= sf.span ? 1u : 0u) << (16 * k + j);
+      }
+    } else {
+      #pragma unroll
+      for (uint32_t j = 0; j < 8; j++) {
+        const uint32_t h = (j & 1u) ? w[j / 2] >> 16 : w[j / 2] & 0xFFFFu;
+        if constexpr (W == 2) {
+          in |= ((h - sf.lo) <= sf.span ? 1u : 0u) << (8 * k + j);
+        } else {
+          const bool m = split_maybe(h, sf), s = split_sure(h, sf);
+          in |= (s ? 1u : 0u) << (8 * k + j);
+          open |= (m && !s ? 1u : 0u) << (8 * k + j);
+        }
+      }
+    }
+  }
+}
+
+/* phase two of a split side: the low-half vectors that hold a needed row,
+   every vector when 16 or more lanes of the wave (lanes, a ballot) need one:
+   k_plane_fcs's dense rule */
+__device__ __forceinline__ void
+fc2_load_lo(const uint4 *__restrict__ lo, const uint64_t (&q)[2],
+            uint64_t n_vec, uint32_t need, unsigned long long lanes,
+            uint4 (&lv)[4]) {
+  const bool dense = __popcll(lanes) >= 16;
+  #pragma unroll
+  for (int k = 0; k < 4; k++) {
+    lv[k] = make_uint4(0, 0, 0, 0);
+    if (dense || ((need >> (8 * k)) & 0xFFu))
+      lv[k] = lo[fc2_vec<4>(q, k, n_vec)];
+  }
+}
+
+/* the rows of a split side whose two halves pass the full test */
+__device__ __forceinline__ uint32_t
+fc2_full(const uint4 (&hv)[4], const uint4 (&lv)[4], const SplitFcArgs &sf) {
+  uint32_t full = 0;
+  #pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t wh[4] = {hv[k].x, hv[k].y, hv[k].z, hv[k].w};
+    const uint32_t wl[4] = {lv[k].x, lv[k].y, lv[k].z, lv[k].w};
+    #pragma unroll
+    for (uint32_t j = 0; j < 8; j++) {
+      const uint32_t h = (j & 1u) ? wh[j / 2] >> 16 : wh[j / 2] & 0xFFFFu;
+      const uint32_t l = (j & 1u) ? wl[j / 2] >> 16 : wl[j / 2] & 0xFFFFu;
+      full |= (split_full_in(h, l, sf) ? 1u : 0u) << (8 * k + j);
+    }
+  }
+  return full;
+}
+
+/* The kernel. Grid-stride over gridDim.x x 256 lanes x 32 rows; b0, the
+ * block's first unit, is uniform, so every lane of a wave takes every
+ * iteration and the ballots below are whole. All vectors of both sides issue
+ * before the first is used; loads are clamped to each plane's last vector and
+ * rows masked by n_rows (live), so the tail slack may be read and never
+ * decides a row.
+ * Phase one classifies both sides. A decided side keeps in ^ invert. A split
+ * side's open rows need their low halves only where they are live and the
+ * other side has not already rejected the row (an open row of the other side
+ * counts as not rejected): need = open & live & (other.open | other.keep).
+ * A wave without a needed row skips phase two; otherwise it loads the low
+ * vectors that hold one (both sides' before either is used) and resolves the
+ * needed rows with split_full_in. An open row that was not needed keeps its
+ * provisional bit, which the other side's zero masks.
+ * count += popc(keepA & keepB & live); the tail is fcn_block_count's. */
+template <int WA, int WB>
+__global__ void __launch_bounds__(256)
+k_plane_fc2(const uint4 *__restrict__ a, const uint4 *__restrict__ a_lo,
+            const uint4 *__restrict__ b, const uint4 *__restrict__ b_lo,
+            uint64_t n_rows, SplitFcArgs sa, SplitFcArgs sb,
+            unsigned long long *__restrict__ cnt_out, uint32_t slot_mask,
+            unsigned int *__restrict__ ticket,
+            unsigned long long *__restrict__ h_out,
+            unsigned long long *__restrict__ stamp, unsigned long long seq) {
+  static_assert(WA <= WB, "the host orders the sides");
+  const unsigned long long t_entry = fcn_entry_clock(stamp);
+  const uint32_t inva = sa.invert ? ~0u : 0u, invb = sb.invert ? ~0u : 0u;
+  const uint64_t n_units = (n_rows + 15) / 16;
+  const uint64_t nva = WA == 1 ? n_units : (n_rows + 7) / 8;
+  const uint64_t nvb = WB == 1 ? n_units : (n_rows + 7) / 8;
+  const uint64_t step = (uint64_t)gridDim.x * 512u;
+  unsigned long long cnt = 0;
+  for (uint64_t b0 = (uint64_t)blockIdx.x * 512u; b0 < n_units; b0 += step) {
+    const uint64_t q[2] = {b0 + threadIdx.x, b0 + 256u + threadIdx.x};
+    uint4 va[4], vb[4];
+    #pragma unroll
+    for (int k = 0; k < (WA == 1 ? 2 : 4); k++)
+      va[k] = a[fc2_vec<WA>(q, k, nva)];
+    #pragma unroll
+    for (int k = 0; k < (WB == 1 ? 2 : 4); k++)
+      vb[k] = b[fc2_vec<WB>(q, k, nvb)];
+    /* every load of both planes issues before the first is used */
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t live = 0;
+    #pragma unroll
+    for (int u = 0; u < 2; u++)
+      if (q[u] < n_units) {
+        const uint64_t left = n_rows - q[u] * 16u;
+        live |= (left < 16u ? (1u << (uint32_t)left) - 1u : 0xFFFFu) << (16 * u);
+      }
+    uint32_t ina, opena, inb, openb;
+    fc2_classify<WA>(va, sa, ina, opena);
+    fc2_classify<WB>(vb, sb, inb, openb);
+    uint32_t keepa = ina ^ inva, keepb = inb ^ invb;
+    if constexpr (WB == 4) {                 /* WA <= WB: some side is split */
+      const uint32_t needa = opena & live & (openb | keepb);   /* 0: WA < 4 */
+      const uint32_t needb = openb & live & (opena | keepa);
+      const unsigned long long la =
+          WA == 4 ? __builtin_amdgcn_ballot_w64(needa != 0) : 0ull;
+      const unsigned long long lb = __builtin_amdgcn_ballot_w64(needb != 0);
+      if ((la | lb) != 0) {                  /* wave-uniform */
+        uint4 wa[4], wb[4];
+        if (WA == 4 && la != 0) fc2_load_lo(a_lo, q, nva, needa, la, wa);
+        if (lb != 0) fc2_load_lo(b_lo, q, nvb, needb, lb, wb);
+        __builtin_amdgcn_sched_barrier(0);
+        if (WA == 4 && la != 0)
+          keepa = (ina | (fc2_full(va, wa, sa) & needa)) ^ inva;
+        if (lb != 0)
+          keepb = (inb | (fc2_full(vb, wb, sb) & needb)) ^ invb;
+      }
+    }
+    cnt += __popc(keepa & keepb & live);
+  }
+  fcn_block_count(cnt, cnt_out, slot_mask, ticket, h_out, stamp, t_entry, seq);
+}
+
 /* IN-list filter+count over a narrow plane of 1 or 2 bytes per row (DESIGN
  * §9o). A stored n = v - base lies in [0, nmax], nmax < 2^(8 sizeof(T)), so
  * the list turns into a bitmap over that domain: 32 B for one byte, 8 KiB for
@@ -1091,6 +1254,53 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
     default:
       return -1;
   }
+  return (int)hipGetLastError();
+}
+
+int dev_plane_fc2_launch(const DevRegion::ColPlane &pa, const SplitFcArgs &sa,
+                         const DevRegion::ColPlane &pb, const SplitFcArgs &sb,
+                         uint64_t n_rows, unsigned long long *d_cnt,
+                         uint32_t n_slots, unsigned int *d_ticket,
+                         unsigned long long *h_out,
+                         unsigned long long *d_stamp, unsigned long long seq,
+                         uint32_t grid_cap, void *stream) {
+  /* dev_plane_fcn_launch's checks on the one-dispatch arguments */
+  if (d_stamp && d_ticket &&
+      d_stamp != (unsigned long long *)d_ticket + COPR_FCN_STAMP_WORD)
+    return -1;
+  if (!pa.nar || !pb.nar || (d_ticket && (!h_out || !seq)) || !n_slots ||
+      n_slots > 64 || (n_slots & (n_slots - 1)) ||
+      (pa.nar_w == 4) != (pa.nar_lo_off != 0) ||
+      (pb.nar_w == 4) != (pb.nar_lo_off != 0) || pa.nar_w > pb.nar_w)
+    return -1;
+  hipStream_t s = (hipStream_t)stream;
+  /* one block per 256 lanes x 32 rows, under dev_plane_fcn_launch's caps: 2048
+     blocks, 768 with a split side. Starting figures, not measured for this
+     kernel; COPR_NARROW_GRID overrides them. A finalizing launch
+     needs a block even over no rows */
+  const uint64_t n_units = (n_rows + 15) / 16;
+  uint64_t nb = (n_units + 511) / 512;
+  const uint64_t cap = grid_cap ? grid_cap : pb.nar_lo_off ? 768u : 2048u;
+  if (nb > cap) nb = cap;
+  if (!nb) nb = 1;
+  const uint4 *a = (const uint4 *)pa.nar, *b = (const uint4 *)pb.nar;
+  const uint4 *a_lo = (const uint4 *)((const uint8_t *)pa.nar + pa.nar_lo_off);
+  const uint4 *b_lo = (const uint4 *)((const uint8_t *)pb.nar + pb.nar_lo_off);
+  const uint32_t mask = n_slots - 1;
+  #define COPR_FC2(WA, WB)                                                   \
+    hipLaunchKernelGGL((k_plane_fc2<WA, WB>), dim3((uint32_t)nb), dim3(256), \
+                       0, s, a, a_lo, b, b_lo, n_rows, sa, sb, d_cnt, mask,  \
+                       d_ticket, h_out, d_stamp, seq)
+  switch (pa.nar_w * 8 + pb.nar_w) {
+    case 1 * 8 + 1: COPR_FC2(1, 1); break;
+    case 1 * 8 + 2: COPR_FC2(1, 2); break;
+    case 1 * 8 + 4: COPR_FC2(1, 4); break;
+    case 2 * 8 + 2: COPR_FC2(2, 2); break;
+    case 2 * 8 + 4: COPR_FC2(2, 4); break;
+    case 4 * 8 + 4: COPR_FC2(4, 4); break;
+    default: return -1;
+  }
+  #undef COPR_FC2
   return (int)hipGetLastError();
 }
 

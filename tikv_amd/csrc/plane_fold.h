@@ -47,6 +47,56 @@ inline void plane_fc_fold(int cmp, int64_t cst, bool uns, bool const_null,
                         ? 1u : 0u;
 }
 
+/* a AND b over one column: both from plane_fc_fold with the same
+   signedness, so the keys share bias. true = *out is the one interval test
+   that keeps exactly the values both keep; false = the conjunction is not one
+   interval (an NE point strictly inside an interval, two different NE
+   points) and the request stays where it was. An inverted test is "never"
+   (the whole range) or an NE point; any other inverted form is refused. */
+inline bool plane_fc_and(const PlaneFcArgs &a, const PlaneFcArgs &b,
+                         PlaneFcArgs *out) {
+  const unsigned long long MAXU = ~0ull;
+  if (a.bias != b.bias) return false;
+  auto never = [&](const PlaneFcArgs &x) {
+    return x.invert && x.lo == 0 && x.span == MAXU;
+  };
+  out->bias = a.bias;
+  out->invert = 0;
+  out->keep_absent = (a.keep_absent && b.keep_absent) ? 1u : 0u;
+  if (never(a) || never(b)) {
+    out->lo = 0; out->span = MAXU; out->invert = 1; out->keep_absent = 0;
+    return true;
+  }
+  if ((a.invert && a.span) || (b.invert && b.span)) return false;
+  if (a.invert && b.invert) {                       /* two NE points */
+    if (a.lo != b.lo) return false;
+    out->lo = a.lo; out->span = 0; out->invert = 1;
+    return true;
+  }
+  unsigned long long lo, hi;
+  if (!a.invert && !b.invert) {                     /* two intervals */
+    const unsigned long long ha = a.lo + a.span, hb = b.lo + b.span;
+    lo = a.lo > b.lo ? a.lo : b.lo;
+    hi = ha < hb ? ha : hb;
+  } else {                                          /* interval, NE point */
+    const PlaneFcArgs &iv = a.invert ? b : a;
+    const unsigned long long p = a.invert ? a.lo : b.lo;
+    lo = iv.lo;
+    hi = iv.lo + iv.span;
+    if (p > lo && p < hi) return false;
+    if (p == lo && p == hi) { lo = 1; hi = 0; }     /* nothing left */
+    else if (p == lo) lo++;
+    else if (p == hi) hi--;
+  }
+  if (lo > hi) {
+    out->lo = 0; out->span = MAXU; out->invert = 1; out->keep_absent = 0;
+    return true;
+  }
+  out->lo = lo;
+  out->span = hi - lo;
+  return true;
+}
+
 /* k_plane_fcn: keep = ((n - lo) <= span) != invert in 32-bit unsigned
    arithmetic over the narrow plane's n = (uint)(v - base). */
 struct NarrowFcArgs {

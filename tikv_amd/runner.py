@@ -599,6 +599,13 @@ class Engine:
         return (self._lib.copr_engine_bucket_launches(self._h),
                 self._lib.copr_engine_bucket_builds(self._h))
 
+    def pair_launches(self):
+        """Narrow launches (narrow_stats()[0] counts them too, split_launches()
+        and bucket_stats() do not) that took k_plane_fc2: count(*) under two
+        conditions over two columns, read from both columns' narrow planes,
+        since the engine was created."""
+        return self._lib.copr_engine_pair_launches(self._h)
+
     def fc_wait_stats(self):
         """(polled, fallbacks): one-dispatch filter+count requests whose end
         the host learnt from the polled sequence word, and those that waited
