@@ -127,6 +127,10 @@ uint64_t    copr_engine_pair_launches(const copr_engine *);
  * requests of every other branch move neither. */
 uint64_t    copr_engine_fc_polled(const copr_engine *);
 uint64_t    copr_engine_fc_fallbacks(const copr_engine *);
+/* Requests of that step that were one launch of one block, which opens and
+ * finalizes the request without a device atomic. Monotonic;
+ * each such request also moves one of the two counters above. */
+uint64_t    copr_engine_fc_solo(const copr_engine *);
 /* IN-list filters over column planes: per-region launches of
  * the set-probe kernel over the wide planes and of the bitmap filter+count
  * kernel over a 1- or 2-byte narrow plane (copr_engine_plane_launches counts

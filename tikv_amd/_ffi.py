@@ -181,6 +181,8 @@ def load_lib():
     lib.copr_engine_fc_polled.argtypes = [C.c_void_p]
     lib.copr_engine_fc_fallbacks.restype = C.c_uint64
     lib.copr_engine_fc_fallbacks.argtypes = [C.c_void_p]
+    lib.copr_engine_fc_solo.restype = C.c_uint64
+    lib.copr_engine_fc_solo.argtypes = [C.c_void_p]
     lib.copr_engine_in_launches.restype = None
     lib.copr_engine_in_launches.argtypes = [C.c_void_p, C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint64)]

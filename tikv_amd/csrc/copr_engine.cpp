@@ -141,6 +141,10 @@ extern "C" uint64_t copr_engine_fc_fallbacks(const copr_engine *eng) {
   return eng ? eng->fc_fallbacks : 0;
 }
 
+extern "C" uint64_t copr_engine_fc_solo(const copr_engine *eng) {
+  return eng ? eng->fc_solo : 0;
+}
+
 extern "C" uint64_t copr_engine_topn_multi_runs(const copr_engine *eng) {
   return eng ? eng->topn_multi_runs : 0;
 }
@@ -2907,11 +2911,12 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
                                   uint32_t n_slots, unsigned int *d_ticket,
                                   unsigned long long *h_out,
                                   unsigned long long *d_stamp,
-                                  unsigned long long seq) -> int {
+                                  unsigned long long seq,
+                                  uint32_t *grid) -> int {
         const int e = dev_plane_inn_launch(*in_nar[rg], pl.sp, in_fa, in_sa[rg],
                                            regions[rg]->dev.n_kv, d_cnt,
                                            n_slots, d_ticket, h_out, d_stamp,
-                                           seq, in_grid, eng->stream);
+                                           seq, in_grid, grid, eng->stream);
         eng->plane_launches++;
         if (in_nar[rg]->nar_lo_off) eng->in_split_launches++;
         else eng->in_bitmap_launches++;
@@ -2922,12 +2927,13 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         fcn_grid = (uint32_t)strtoul(g, nullptr, 10);
       /* one launch of a range request over a region's narrow plane or, for two
          conditions over two columns, planes; its counters.
-         *bytes = what the launch can read */
+         *bytes = what the launch can read, *grid = its blocks */
       auto narrow_launch = [&](uint32_t rg, unsigned long long *d_cnt,
                                uint32_t n_slots, unsigned int *d_ticket,
                                unsigned long long *h_out,
                                unsigned long long *d_stamp,
-                               unsigned long long seq, uint64_t *bytes) -> int {
+                               unsigned long long seq, uint64_t *bytes,
+                               uint32_t *grid) -> int {
         const NarrowUse &u = nuse[rg];
         const uint64_t n_kv = regions[rg]->dev.n_kv;
         int e;
@@ -2936,14 +2942,14 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         if (u.p2) {
           e = dev_plane_fc2_launch(*u.p, u.sf, *u.p2, u.sf2, n_kv, d_cnt,
                                    n_slots, d_ticket, h_out, d_stamp, seq,
-                                   fcn_grid, eng->stream);
+                                   fcn_grid, grid, eng->stream);
           eng->pair_launches++;
           if (bytes) *bytes += n_kv * (u.p->nar_w + u.p2->nar_w);
           return e;
         }
         e = dev_plane_fcn_launch(*u.p, u.nf, u.sf, u.bucket ? &u.ba : nullptr,
                                  n_kv, d_cnt, n_slots, d_ticket, h_out,
-                                 d_stamp, seq, fcn_grid, eng->stream);
+                                 d_stamp, seq, fcn_grid, grid, eng->stream);
         if (u.bucket) eng->bucket_launches++;
         else if (u.p->nar_lo_off) eng->split_launches++;
         if (bytes) *bytes += n_kv * u.p->nar_w;
@@ -3009,6 +3015,7 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
         if (!++eng->fcn_seq) ++eng->fcn_seq;
         const unsigned long long seq = eng->fcn_seq;
         uint64_t stream_bytes = 0;
+        uint32_t grid = 0;
         for (uint32_t rg = 0; rg < n_regions; rg++) {
           const bool last = rg + 1 == n_regions;
           int e;
@@ -3016,19 +3023,23 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             e = in_narrow_launch(rg, d_cnt, COPR_FCN_SLOTS,
                                  last ? d_ticket : nullptr,
                                  last ? eng->h_fcn_out : nullptr,
-                                 rg == 0 ? d_stamp : nullptr, seq);
+                                 rg == 0 ? d_stamp : nullptr, seq, &grid);
             stream_bytes += regions[rg]->dev.n_kv * in_nar[rg]->nar_w;
           } else {
             e = narrow_launch(rg, d_cnt, COPR_FCN_SLOTS,
                               last ? d_ticket : nullptr,
                               last ? eng->h_fcn_out : nullptr,
-                              rg == 0 ? d_stamp : nullptr, seq, &stream_bytes);
+                              rg == 0 ? d_stamp : nullptr, seq, &stream_bytes,
+                              &grid);
           }
           if (e) {
             eng->fcn_dirty = true;
             return SET_ERR(COPR_ERR_INTERNAL, "narrow plane launch failed");
           }
         }
+        /* ticket, stamp and one block: the kernel's own condition for the
+           solo tail (fcn_block_count) */
+        if (n_regions == 1 && grid == 1) eng->fc_solo++;
         /* How long to spin before handing the wait to the runtime: the bytes
            the launches can read (a split plane's both halves) at 50 GB/s, a
            hundredth of the slowest rate a plane has shown (5
@@ -3080,12 +3091,12 @@ extern "C" copr_status copr_dag_run(copr_engine *eng, const CoprDagRequest *req,
             /* a narrow region beside regions that are not: same kernel, the
                count joins the other regions' in the usual accumulator */
             e = narrow_launch(rg, &d_acc[0].cnt, 1, nullptr, nullptr, nullptr,
-                              0, nullptr);
+                              0, nullptr, nullptr);
           } else if (in_planes && plane_set_used(psets[rg])) {
             if (in_nar[rg]) {
               /* one slot, no ticket: the count joins the other regions' */
               e = in_narrow_launch(rg, &d_acc[0].cnt, 1, nullptr, nullptr,
-                                   nullptr, 0);
+                                   nullptr, 0, nullptr);
             } else {
               e = dev_plane_in_launch(sp, psets[rg], in_fa, regions[rg]->dev,
                                       d_acc, in_grid, eng->stream);

@@ -402,10 +402,13 @@ bool dev_plane_fc_shape(const ScanPlan &plan, const PlaneSet &ps,
  * non-null d_ticket the launch finalizes: its last block stores that sum,
  * the request's wall-clock ticks and last of all seq (never 0) to the three
  * words at h_out (fc_wait.h FCW_*; fine-grained pinned host memory) and
- * zeroes the count words, *d_ticket and the stamp word.
+ * leaves the count words, *d_ticket and the stamp word zero (DESIGN §9e,
+ * §9n, §9s).
  * A non-null d_stamp marks the launch that opens a request: its block 0
  * leaves the wall clock it read at entry in that word, which is the u64
- * COPR_FCN_STAMP_WORD behind the ticket. grid_cap 0 = the default grid. A
+ * COPR_FCN_STAMP_WORD behind the ticket. grid_cap 0 = the default grid;
+ * *grid_out (may be null) = the blocks launched, from which the caller knows
+ * that a launch with ticket, stamp and one block took the solo tail. A
  * split plane (width 4) takes k_plane_fcs and sf, the others k_plane_fcn<T>
  * and nf. A non-null ba (bucket_fc_fold over the plane's bucket index, DESIGN
  * §9q) sends a split plane to k_plane_fcb: one launch over the edge buckets'
@@ -420,7 +423,7 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
                          uint32_t n_slots, unsigned int *d_ticket,
                          unsigned long long *h_out,
                          unsigned long long *d_stamp, unsigned long long seq,
-                         uint32_t grid_cap, void *stream);
+                         uint32_t grid_cap, uint32_t *grid_out, void *stream);
 /* Two conditions over two columns. dev_plane_fc2_shape: does the
  * request, count(*) under cmp(col a, const) AND cmp(col b, const) over two
  * distinct int columns, fit k_plane_fc2 on this wiring? On true *fa and *fb
@@ -438,7 +441,7 @@ int dev_plane_fc2_launch(const DevRegion::ColPlane &pa, const SplitFcArgs &sa,
                          uint32_t n_slots, unsigned int *d_ticket,
                          unsigned long long *h_out,
                          unsigned long long *d_stamp, unsigned long long seq,
-                         uint32_t grid_cap, void *stream);
+                         uint32_t grid_cap, uint32_t *grid_out, void *stream);
 /* simple aggregates (mode 1) over column planes instead of the row bytes */
 int dev_plane_agg_launch(const ScanPlan &plan, const PlaneSet &ps,
                          const DevRegion &rgn, SimpleAggAcc *d_simple,
@@ -466,7 +469,7 @@ int dev_plane_inn_launch(const DevRegion::ColPlane &p, const ScanPlan &plan,
                          uint32_t n_slots, unsigned int *d_ticket,
                          unsigned long long *h_out,
                          unsigned long long *d_stamp, unsigned long long seq,
-                         uint32_t grid_cap, void *stream);
+                         uint32_t grid_cap, uint32_t *grid_out, void *stream);
 /* int-key hash aggregation (mode 2) over column planes; the
    plan carries table_size and lds_agg_slots as for dev_scan_launch */
 int dev_plane_hash_launch(const ScanPlan &plan, const PlaneSet &ps,
@@ -719,6 +722,9 @@ struct copr_engine {
      (copr_engine_fc_polled / _fc_fallbacks) */
   uint64_t fc_polled = 0;
   uint64_t fc_fallbacks = 0;
+  /* of those, requests of one launch whose grid was one block: the solo tail
+     (copr_engine_fc_solo) */
+  uint64_t fc_solo = 0;
 };
 
 struct copr_region {

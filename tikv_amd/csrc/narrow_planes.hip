@@ -290,10 +290,16 @@ static DevRegion::ColPlane *narrow_plane(DevRegion &rgn, int64_t col_id,
  * draws its ticket, by the rule of the count add: an atomic with a return
  * value, waited for; relaxed atomics to two addresses are not ordered
  * otherwise. The finalizing block takes the stamp back, reads the clock again
- * and stores to h_out, fine-grained pinned host memory the host polls:
- * FCW_COUNT and FCW_TICKS, a system-scope fence, then seq in FCW_SEQ, which
- * the host waits for, and a second fence. seq is never 0 and new for every
- * request.
+ * and hands over (fcn_hand_over) to h_out, fine-grained pinned host memory
+ * the host polls.
+ * Solo: a launch with a stamp, a ticket and a grid of one block
+ * opens the request, finalizes it and has nobody to order against, so its
+ * block sum is the request's count and t_entry its stamp: no atomic, no
+ * second barrier, straight to the hand-over. stamp && ticket is the right
+ * condition: an earlier launch of the same request would have put its count
+ * into the count words, and such a request's last launch has no stamp; the
+ * words a solo launch leaves alone are zero when it starts and stay zero,
+ * which is the state the ticket path leaves behind.
  * Assumption: block 0 starts no later than any other block's first load
  * matters. Workgroups are handed out in index order, so block 0 is in the
  * first wave of dispatches; the time between the dispatch packet and block
@@ -305,6 +311,25 @@ fcn_entry_clock(const unsigned long long *stamp) {
   return (stamp && blockIdx.x == 0) ? wall_clock64() : 0ull;
 }
 
+/* The hand-over of a one-dispatch request to h_out, fine-grained
+ * pinned host memory the host polls: FCW_COUNT and FCW_TICKS, a system-scope
+ * fence, then seq in FCW_SEQ, which the host waits for, and a second fence.
+ * A clock that did not advance reads as "no time", never as a wrapped
+ * difference. seq is never 0 and new for every request. */
+__device__ __forceinline__ void
+fcn_hand_over(unsigned long long *__restrict__ h_out, unsigned long long tot,
+              unsigned long long t0, unsigned long long t1,
+              unsigned long long seq) {
+  __hip_atomic_store(h_out + FCW_COUNT, tot, __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(h_out + FCW_TICKS, t1 > t0 ? t1 - t0 : 0ull,
+                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __threadfence_system();
+  __hip_atomic_store(h_out + FCW_SEQ, seq, __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_SYSTEM);
+  __threadfence_system();
+}
+
 __device__ __forceinline__ void
 fcn_block_count(unsigned long long cnt, unsigned long long *__restrict__ cnt_out,
                 uint32_t slot_mask, unsigned int *__restrict__ ticket,
@@ -313,10 +338,19 @@ fcn_block_count(unsigned long long cnt, unsigned long long *__restrict__ cnt_out
                 unsigned long long t_entry, unsigned long long seq) {
   __shared__ unsigned long long s_cnt[4];
   __shared__ unsigned int s_last;
+  /* block-uniform, from kernel arguments and the grid alone */
+  const bool solo = ticket && stamp && gridDim.x == 1;
   for (int off = 32; off > 0; off >>= 1)
     cnt += (unsigned long long)__shfl_down((long long)cnt, off, 64);
   if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = cnt;
   __syncthreads();
+  if (solo) {
+    if (threadIdx.x == 0) {
+      const unsigned long long tot = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+      fcn_hand_over(h_out, tot, t_entry, wall_clock64(), seq);
+    }
+    return;
+  }
   if (threadIdx.x == 0) {
     const unsigned long long b = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     unsigned long long *slot =
@@ -365,16 +399,7 @@ fcn_block_count(unsigned long long cnt, unsigned long long *__restrict__ cnt_out
   if (threadIdx.x == 0) {
     const unsigned long long t1 = wall_clock64();
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(h_out + FCW_COUNT, tot, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-    /* a clock that did not advance reads as "no time", never as a wrapped
-       difference */
-    __hip_atomic_store(h_out + FCW_TICKS, t1 > t0 ? t1 - t0 : 0ull,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __threadfence_system();
-    __hip_atomic_store(h_out + FCW_SEQ, seq, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-    __threadfence_system();
+    fcn_hand_over(h_out, tot, t0, t1, seq);
   }
 }
 
@@ -1120,7 +1145,8 @@ int dev_plane_inn_launch(const DevRegion::ColPlane &p, const ScanPlan &plan,
                          uint32_t n_slots, unsigned int *d_ticket,
                          unsigned long long *h_out,
                          unsigned long long *d_stamp, unsigned long long seq,
-                         uint32_t grid_cap, void *stream) {
+                         uint32_t grid_cap, uint32_t *grid_out,
+                         void *stream) {
   /* dev_plane_fcn_launch's checks on the one-dispatch arguments */
   if (d_stamp && d_ticket &&
       d_stamp != (unsigned long long *)d_ticket + COPR_FCN_STAMP_WORD)
@@ -1153,6 +1179,7 @@ int dev_plane_inn_launch(const DevRegion::ColPlane &p, const ScanPlan &plan,
   const uint64_t cap = grid_cap ? grid_cap : light ? 768u : 2048u;
   if (nb > cap) nb = cap;
   if (!nb || (split && (sa.none || fa.never))) nb = 1;
+  if (grid_out) *grid_out = (uint32_t)nb;
   const uint4 *data = (const uint4 *)p.nar;
   const uint32_t mask = n_slots - 1;
   const uint32_t in_slots = plan.in_mask + 1;
@@ -1184,7 +1211,8 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
                          uint32_t n_slots, unsigned int *d_ticket,
                          unsigned long long *h_out,
                          unsigned long long *d_stamp, unsigned long long seq,
-                         uint32_t grid_cap, void *stream) {
+                         uint32_t grid_cap, uint32_t *grid_out,
+                         void *stream) {
   /* a stamp is taken back by a finalizing launch alone, and its word sits
      behind the ticket */
   if (d_stamp && d_ticket &&
@@ -1207,6 +1235,7 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
   const uint64_t cap = grid_cap ? grid_cap : p.nar_lo_off ? 768u : 2048u;
   if (nb > cap) nb = cap;
   if (!nb) nb = 1;
+  if (grid_out) *grid_out = (uint32_t)nb;
   const uint4 *data = (const uint4 *)p.nar;
   const uint32_t mask = n_slots - 1;
   if (ba) {
@@ -1228,6 +1257,13 @@ int dev_plane_fcn_launch(const DevRegion::ColPlane &p, const NarrowFcArgs &nf,
     uint64_t bb = (vecs + 256u * 4 - 1) / (256u * 4);
     if (bb > cap) bb = cap;
     if (!bb) bb = 1;
+    /* a launch that opens and finalizes takes one block for up to two
+       iterations (2048 vectors): the solo tail's second load round trip
+       is shorter than the ticketed tail's three atomic ones. Measured at
+       8193 and 16384 slice rows, behind from 32768 on;
+       COPR_NARROW_GRID=2 still gives two blocks */
+    if (!grid_cap && d_stamp && d_ticket && bb == 2) bb = 1;
+    if (grid_out) *grid_out = (uint32_t)bb;
     const unsigned long long add =
         ba->invert ? n_rows - ba->sure - slice_rows : ba->sure;
     hipLaunchKernelGGL(k_plane_fcb, dim3((uint32_t)bb), dim3(256), 0, s,
@@ -1263,7 +1299,8 @@ int dev_plane_fc2_launch(const DevRegion::ColPlane &pa, const SplitFcArgs &sa,
                          uint32_t n_slots, unsigned int *d_ticket,
                          unsigned long long *h_out,
                          unsigned long long *d_stamp, unsigned long long seq,
-                         uint32_t grid_cap, void *stream) {
+                         uint32_t grid_cap, uint32_t *grid_out,
+                         void *stream) {
   /* dev_plane_fcn_launch's checks on the one-dispatch arguments */
   if (d_stamp && d_ticket &&
       d_stamp != (unsigned long long *)d_ticket + COPR_FCN_STAMP_WORD)
@@ -1283,6 +1320,7 @@ int dev_plane_fc2_launch(const DevRegion::ColPlane &pa, const SplitFcArgs &sa,
   const uint64_t cap = grid_cap ? grid_cap : pb.nar_lo_off ? 768u : 2048u;
   if (nb > cap) nb = cap;
   if (!nb) nb = 1;
+  if (grid_out) *grid_out = (uint32_t)nb;
   const uint4 *a = (const uint4 *)pa.nar, *b = (const uint4 *)pb.nar;
   const uint4 *a_lo = (const uint4 *)((const uint8_t *)pa.nar + pa.nar_lo_off);
   const uint4 *b_lo = (const uint4 *)((const uint8_t *)pb.nar + pb.nar_lo_off);

@@ -616,6 +616,11 @@ class Engine:
         return (self._lib.copr_engine_fc_polled(self._h),
                 self._lib.copr_engine_fc_fallbacks(self._h))
 
+    def fc_solo(self):
+        """requests of the one-dispatch filter+count step that were one launch
+        of one block (the atomic-free tail)"""
+        return self._lib.copr_engine_fc_solo(self._h)
+
     def in_stats(self):
         """(wide launches, bitmap launches): per-region launches of the
         IN-list kernels, k_plane_in over the wide planes and k_plane_inb over
